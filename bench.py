@@ -19,20 +19,36 @@ Other BASELINE.json configs (`--config`, not what the driver runs):
   c5  the full dividend sheet (4 bond penalties x 14 cases x 9 versions =
       504 runs) through generate_total_dividends_tables.
 
-Prints ONE JSON line (rank 0) with the driver's fields plus
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+headline figure needs: it sets up, warms up, times the N steps, writes the
+outputs of the last timed step if `--dump-outputs DIR` is given, and prints
+ONE JSON line (rank 0) with the driver's fields (metric, value, unit,
+ms_per_step, ...) plus
   roofline      SURVEY §8d step roofline: achieved = scenario-epochs/s per GPU x
                 BYTES(V,M) (the fp32 epoch-step contract, 12,617,728 B at
                 256 x 4096), frac = achieved / 8 TB/s; traffic = the rocprofv3
                 FETCH_SIZE + WRITE_SIZE bytes of one step (committed PMC passes of
-                this exact workload, profiles/r05/pmc_traffic.json), and
+                this exact workload, profiles/r05/pmc_traffic.json).
+Everything that takes runs of its own is behind `--full`, which adds
+  phases        per-phase device time (HIP-event passes after the timed steps), and
                 roofline.kernel = the dominant kernel (k_bonds_elem at c2):
-                algorithmic bytes per launch / its HIP-event launch time;
+                algorithmic bytes per launch / its HIP-event launch time
+                (c3: its VALU issue roofline);
   cpu_baseline  the torch-CPU restatement of the epoch (oracle/torch_cpu.py,
                 bit-identical to the reference goldens) on the host cores of
                 this box: vectorised (value) and reference-structured (per-column
                 Python bisection, as yumas.py runs it);
   also          (default c2 run) the same line's numbers for "Yuma 4 liquid",
                 the second c2 version of SURVEY §7, on the same resident inputs.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step
+(the arrays a caller of that step receives: Dn, C, I, B_final, B_hist for
+c2 / c3 / c4, the sheet's tables for c5; rank 0's own outputs under
+torchrun) as DIR/<name>.npy, float32 or float64, at most 64 MB in all: an
+array that does not fit its share is written as a fixed, seeded sample of
+its elements (the line's "dump_outputs" field says which, and how). The inputs are
+seeded, so two builds run with the same arguments can be compared output
+for output.
 
 `--gpus N` without torchrun re-launches itself under torch.distributed.run
 with N local ranks (before anything touches a GPU).
@@ -277,6 +293,56 @@ def cpu_baseline(variant: str, W_dev, S_dev, cfgs: list, seconds: float, warmup:
     }
 
 
+DUMP_BUDGET = 56 * 2**20  # bytes of array data per --dump-outputs (under 64e6 with the .npy headers)
+DUMP_SEED = 0x5EEDD0
+
+
+def dump_outputs(directory: str, arrays: dict) -> dict:
+    """--dump-outputs: write each array (device tensor or numpy) as
+    <directory>/<name>.npy in float32 (float64 for anything that is not
+    float32), DUMP_BUDGET bytes in all. The budget is dealt smallest array
+    first; an array larger than its share is written as a sample of its
+    flattened elements at sorted indices drawn from a generator seeded by
+    DUMP_SEED and the array's position (the same indices on every run of the
+    same arguments). Returns {name: shape, dtype and sampling} for the line."""
+    os.makedirs(directory, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].numel() if torch.is_tensor(arrays[k]) else arrays[k].size, k))
+    left = DUMP_BUDGET
+    manifest = {}
+    for i, name in enumerate(names):
+        a = arrays[name]
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.ascontiguousarray(a))
+        if a.dtype != torch.float32:
+            a = a.to(torch.float64)
+        flat = a.contiguous().reshape(-1)
+        share = left // (len(names) - i)
+        n, item = flat.numel(), flat.element_size()
+        entry = {"shape": list(a.shape), "dtype": str(flat.dtype).replace("torch.", ""), "sampled": False}
+        if n * item > share:
+            rng = np.random.default_rng([DUMP_SEED, sorted(arrays).index(name)])
+            idx = np.unique(rng.integers(0, n, size=share // item, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            entry.update(sampled=True, count=int(idx.size), seed=[DUMP_SEED, sorted(arrays).index(name)],
+                         draws=share // item,
+                         sample="flattened elements at np.unique(default_rng(seed).integers(0, numel, draws))")
+        else:
+            flat = flat.reshape(a.shape)
+        host = flat.cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), host)
+        left -= host.nbytes
+        manifest[name] = entry
+    return manifest
+
+
+def keep_last(step, cell: list):
+    """step, with its return value kept in cell[0] (for --dump-outputs of a
+    step that returns fresh results)."""
+    def kept():
+        cell[0] = step()
+    return kept
+
+
 PREWARM_S = 1.0
 # torch.distributed backend of the N-rank run: "nccl" (RCCL over xGMI, one GPU
 # per rank); "gloo" only to rehearse the multi-rank path on a one-GPU box
@@ -374,10 +440,12 @@ def consensus_classes(params: list) -> int:
 
 
 def engine_line(args, variant: int, params: list, W, S, world: int, dist: bool, workload: dict,
-                shared: bool = False) -> dict:
+                shared: bool = False, dump_dir: str | None = None) -> dict:
     """Time one engine configuration on resident inputs and build its line:
-    the step (graph replay of the whole E-epoch run), per-phase HIP-event
-    device time, the §8d step roofline and the dominant kernel's roofline."""
+    the step (graph replay of the whole E-epoch run) and the §8d step
+    roofline; with --full also the per-phase HIP-event device time and the
+    dominant kernel's roofline (runs of their own, after the timed steps).
+    dump_dir: write the outputs of the last timed step there (dump_outputs)."""
     from yuma_simulation._internal import engine
 
     dev = W.device
@@ -406,6 +474,42 @@ def engine_line(args, variant: int, params: list, W, S, world: int, dist: bool, 
     elapsed = timed(step, args.warmup, args.steps, dist, dev)
     units = E * N  # scenario-epochs per step per GPU
     value = float(units) * world * args.steps / elapsed
+    if dump_dir is not None:
+        # `out` holds what the last timed step wrote (the buffers of the
+        # capture, or of the direct launch)
+        dumped = dump_outputs(dump_dir, out)
+
+    contract = contract_bytes(V, M, variant)
+    per_gpu = value / world
+    equivalent = per_gpu * contract / 1e9
+    key = {k: workload[k] for k in ("V", "M", "epochs", "scenarios_per_gpu", "version", "bond_history")}
+    pmc = load_traffic(key)
+    traffic = None if pmc is None else round(sum(pmc.values()) * units)
+    line = base_line(args, world, value, "scenario-epochs/s", elapsed, "weak", workload)
+    if dump_dir is not None:
+        line["dump_outputs"] = dumped
+    step_roofline = {
+        "bound": "hbm",
+        "achieved": round(equivalent, 1),
+        "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s",
+        "frac": round(equivalent / HBM_PEAK_GBPS, 4),
+        "traffic": traffic,
+        "definition": (f"SURVEY 8d step roofline: scenario-epochs/s per GPU x BYTES(V,M) = {contract:,.0f} B "
+                       "(read W, B, S; write B, Dn, C, I) / 8 TB/s; traffic = rocprofv3 FETCH_SIZE + "
+                       f"WRITE_SIZE bytes of one step ({os.path.relpath(TRAFFIC_JSON, ROOT)})"),
+        "contract_bytes_per_step": contract * units,
+    }
+    if not args.full:
+        # a plain run: the step roofline follows from the timed steps alone;
+        # the c3 sweep's VALU roofline needs its dominant kernel's time (--full)
+        if graph is not None:
+            graph.close()
+        if not shared:
+            line["roofline"] = step_roofline
+        else:
+            line["config"]["consensus_classes"] = consensus_classes(params)
+        return line
 
     # per-phase device time from HIP events recorded on the launch stream
     # (yuma_run_profiled: separate, untimed runs of the same step)
@@ -436,13 +540,6 @@ def engine_line(args, variant: int, params: list, W, S, world: int, dist: bool, 
     dom_ms = float(phases[dom]) / launches
     k_achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
 
-    contract = contract_bytes(V, M, variant)
-    per_gpu = value / world
-    equivalent = per_gpu * contract / 1e9
-    key = {k: workload[k] for k in ("V", "M", "epochs", "scenarios_per_gpu", "version", "bond_history")}
-    pmc = load_traffic(key)
-    traffic = None if pmc is None else round(sum(pmc.values()) * units)
-    line = base_line(args, world, value, "scenario-epochs/s", elapsed, "weak", workload)
     kernel = {
         "name": dom_kernel,
         "launches_per_step": launches,
@@ -454,19 +551,7 @@ def engine_line(args, variant: int, params: list, W, S, world: int, dist: bool, 
         "timing": "HIP events on the launch stream around the kernel (yuma_run_profiled)",
     }
     if not shared:
-        line["roofline"] = {
-            "bound": "hbm",
-            "achieved": round(equivalent, 1),
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": round(equivalent / HBM_PEAK_GBPS, 4),
-            "traffic": traffic,
-            "definition": (f"SURVEY 8d step roofline: scenario-epochs/s per GPU x BYTES(V,M) = {contract:,.0f} B "
-                           "(read W, B, S; write B, Dn, C, I) / 8 TB/s; traffic = rocprofv3 FETCH_SIZE + "
-                           f"WRITE_SIZE bytes of one step ({os.path.relpath(TRAFFIC_JSON, ROOT)})"),
-            "contract_bytes_per_step": contract * units,
-            "kernel": kernel,
-        }
+        line["roofline"] = dict(step_roofline, kernel=kernel)
     else:
         # one shared input trajectory: the sweep scan re-reads W from the
         # caches and is bound by VALU issue, not HBM: the
@@ -556,14 +641,15 @@ def bench_engine(args, world: int, rank: int, dist: bool) -> dict:
                 "bond_history": hist, "launch": "direct" if args.no_graph else "hipGraph replay",
                 "parallelism": f"scenario-sharded x{world}" if world > 1 else "single GPU"}
 
-    line = engine_line(args, variant, params, W, S, world, dist, workload_of(args.version, liquid), shared=shared)
-    if args.config == "c2" and not args.no_also:
+    line = engine_line(args, variant, params, W, S, world, dist, workload_of(args.version, liquid), shared=shared,
+                       dump_dir=args.dump_outputs if rank == 0 else None)
+    if args.full and args.config == "c2" and not args.no_also:
         # SURVEY §7 "Config 2 naming": c2 is quoted for Yuma 3 AND Yuma 4 liquid
         v4 = "Yuma 4 (Rhef+relative bonds) - liquid alpha on"
         p4 = [engine.make_params(4, YumaConfig(yuma_params=YumaParams(liquid_alpha=True)))] * N
         l4 = engine_line(args, 4, p4, W, S, world, dist, workload_of(v4, True))
         line["also"] = {v4: {k: l4[k] for k in ("value", "unit", "ms_per_step", "roofline", "phases", "config")}}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         if args.config == "c3":
             line["cpu_baseline"] = cpu_baseline("yuma4" if variant == 4 else "yuma3", W, S, cfgs[:8], 10.0, 1, 1,
                                                 "c3: first 8 sweep scenarios")
@@ -600,7 +686,15 @@ def bench_wide(args, world: int, rank: int, dist: bool) -> dict:
         def step():
             return engine.run(variant, params, W, S, want_hist=hist, workspace=ws)
 
-    elapsed = timed(step, args.warmup, args.steps, dist, dev)
+    last = [None]
+    elapsed = timed(keep_last(step, last) if args.dump_outputs else step, args.warmup, args.steps, dist, dev)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's result; sharded: rank 0's columns of C, I and B
+        # (WideResult holds them as one-shard lists)
+        got = {k: getattr(last[0], k) for k in ("Dn", "C", "I", "B_final", "B_hist")}
+        dumped = dump_outputs(args.dump_outputs, {k: v[0] if isinstance(v, list) else v for k, v in got.items()
+                                                  if v is not None})
+    last[0] = None
     value = float(E) * args.steps / elapsed  # one subnet: total work fixed
     per_gpu_bytes = contract_bytes(V, len(cols), variant) * E * args.steps / elapsed / 1e9
     layout = f"miner columns sharded x{world}" if dist else "unsharded, one GPU"
@@ -609,6 +703,8 @@ def bench_wide(args, world: int, rank: int, dist: bool) -> dict:
                 "parallelism": (f"miner-column sharded x{world} (all-gather of per-shard partials)" if dist
                                 else "single GPU, unsharded engine")}
     line = base_line(args, world, value, "scenario-epochs/s", elapsed, "strong", workload)
+    if args.dump_outputs and rank == 0:
+        line["dump_outputs"] = dumped
     pmc = load_traffic({k: workload[k] for k in ("V", "M", "epochs", "scenarios_per_gpu", "version",
                                                   "bond_history")}) if world == 1 else None
     line["roofline"] = {"bound": "hbm", "achieved": round(per_gpu_bytes, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -616,7 +712,7 @@ def bench_wide(args, world: int, rank: int, dist: bool) -> dict:
                         "traffic": None if pmc is None else round(sum(pmc.values()) * E),
                         "definition": "SURVEY 8d step roofline per GPU: BYTES(V, M/world) x epochs/s / 8 TB/s "
                                       "(all stages and exchanges inside the wall time)"}
-    if not dist:
+    if not dist and args.full:
         # per-phase device time of the same run (HIP events, yuma_run_profiled)
         # and the dominant kernel's roofline, as for c2
         buf = [0.0] * len(engine.PHASES)
@@ -638,7 +734,7 @@ def bench_wide(args, world: int, rank: int, dist: bool) -> dict:
             "traffic": None if pmc is None or dk not in pmc else round(pmc[dk] * E),
             "timing": "HIP events on the launch stream around the kernel (yuma_run_profiled)"}
         line["phases"] = phases
-    if rank == 0 and not args.no_cpu_baseline and variant in (3, 4):
+    if rank == 0 and args.full and not args.no_cpu_baseline and variant in (3, 4):
         Wc = engine.synth_weights(args.seed, 3, 1, V, M)  # the full-width first epochs, for the CPU
         line["cpu_baseline"] = cpu_baseline({3: "yuma3", 4: "yuma4"}[variant], Wc, S, [YumaConfig()], 10.0, 1, 0,
                                             f"c4: {args.version} at {V}x{M}")
@@ -673,16 +769,30 @@ def bench_sheet(args, world: int, rank: int, dist: bool) -> dict:
         def step():
             return generate_total_dividends_tables(cases, versions, hypers)
 
-    elapsed = timed(step, args.warmup, args.steps, dist, dev)
+    last = [None]
+    elapsed = timed(keep_last(step, last) if args.dump_outputs else step, args.warmup, args.steps, dist, dev)
+    if args.dump_outputs and rank == 0:
+        if dist:
+            # rank 0's share of the runs: every run's per-validator dividend lists, in run order
+            arrays = {"dividends": np.array([x for d, _, _ in last[0] for col in d.values() for x in col],
+                                            dtype=np.float64)}
+        else:
+            # one table per bond penalty: its numeric columns, [cases, 3 validators x versions]
+            arrays = {f"table_{i}": df.drop(columns=["Case"]).to_numpy(dtype=np.float64)
+                      for i, df in enumerate(last[0])}
+        dumped = dump_outputs(args.dump_outputs, arrays)
+    last[0] = None
     value = units * args.steps / elapsed
     workload = {"workload": f"c5: dividend sheet, {len(runs)} runs (4 bond penalties x {len(cases)} cases x "
                             f"{len(versions)} versions), {units} scenario-epochs", "runs": len(runs),
                 "scenario_epochs": units, "parallelism": f"runs sharded x{world}" if world > 1 else "single GPU"}
     line = base_line(args, world, value, "scenario-epochs/s", elapsed, "strong", workload)
+    if args.dump_outputs and rank == 0:
+        line["dump_outputs"] = dumped
     line["data"] = "the reference's built-in cases (cases.py)"
     line["roofline"] = {"bound": "latency", "kernel": "whole sheet (3x2 matrices: launch/host bound)",
                         "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = sheet_cpu_baseline(len(runs), units)
     return line
 
@@ -763,11 +873,17 @@ def main():
     ap.add_argument("--no-graph", action="store_true",
                     help="c2/c3: launch each step directly instead of replaying a captured hipGraph")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: larger arrays as a fixed seeded sample)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-phase HIP-event times and "
+                         "the dominant kernel's roofline, the c2 Yuma 4 liquid companion line, the CPU baselines")
     ap.add_argument("--cpu-structured-epochs", type=int, default=10,
-                    help="c2: timed epochs of the reference-structured CPU baseline (0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="c2: skip the Yuma 4 liquid companion line")
-    ap.add_argument("--profile-reps", type=int, default=3)
+                    help="--full, c2: timed epochs of the reference-structured CPU baseline (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="--full, c2: skip the Yuma 4 liquid companion line")
+    ap.add_argument("--profile-reps", type=int, default=3, help="--full: HIP-event passes per phase figure")
     args = ap.parse_args()
     E, V, M, N, version, hist = DEFAULTS[args.config]
     args.epochs = args.epochs or E

@@ -472,3 +472,61 @@ def test_shared_input_multiclass_small_shapes(V, M, variant):
     np.testing.assert_array_equal(a.C[:, 0].cpu().numpy(), ref["C"])
     assert_close(a.Dn[:, 0].cpu().numpy(), ref["Dn"], what="Dn")
     assert_close(a.B_hist[:, 0].cpu().numpy(), ref["B"], what="B")
+
+
+def _bench_line(monkeypatch, capsys, *argv) -> dict:
+    """bench.main() in this process with the given command line (the clock
+    ramp cut short: the figures are not what is checked); its JSON line."""
+    import json
+    import sys
+
+    monkeypatch.setattr(bench, "PREWARM_S", 0.01)
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    capsys.readouterr()
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_the_timed_step_and_full_adds_the_rest(tmp_path, monkeypatch, capsys):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` prints the driver's
+    fields from the N timed steps alone (no phase passes, companion line or
+    CPU baseline); --dump-outputs writes what the last timed step computed
+    (bitwise engine.run on the same seeded inputs; the bond history that does
+    not fit its share as the recorded sample); --full adds the rest."""
+    small = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--epochs", "6", "--validators", "96",
+             "--miners", "520"]
+    d = tmp_path / "dump"
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 512 * 1024)
+    line = _bench_line(monkeypatch, capsys, *small, "--dump-outputs", str(d))
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["unit"] == "scenario-epochs/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["metric"] == bench.METRIC
+    assert line["value"] == pytest.approx(6 * 1e3 / line["ms_per_step"], rel=1e-2)
+    assert not {"phases", "also", "cpu_baseline"} & set(line) and "kernel" not in line["roofline"]
+
+    E, V, M = 6, 96, 520
+    W = engine.synth_weights(0x5EED0002, E, 1, V, M)
+    S = torch.from_numpy(synth.stakes(0x5EED0002, E, 1, V)).to(W.device)
+    ref = engine.run(engine.VARIANT_YUMA3, [engine.make_params(engine.VARIANT_YUMA3, YumaConfig())], W, S,
+                     want_hist=True)
+    torch.cuda.synchronize()
+    info = line["dump_outputs"]
+    assert sorted(info) == ["B_final", "B_hist", "C", "Dn", "I"]
+    for name in info:
+        got = np.load(d / (name + ".npy"))
+        want = getattr(ref, name).cpu().numpy()
+        assert got.dtype == np.float32 and info[name]["shape"] == list(want.shape)
+        if info[name]["sampled"]:
+            idx = np.unique(np.random.default_rng(info[name]["seed"]).integers(
+                0, want.size, size=info[name]["draws"], dtype=np.int64))
+            want = want.reshape(-1)[idx]
+        np.testing.assert_array_equal(got, want, err_msg=name)
+    assert [k for k in info if info[k]["sampled"]] == ["B_hist"]
+
+    full = _bench_line(monkeypatch, capsys, *small, "--full", "--no-cpu-baseline", "--profile-reps", "1")
+    assert full["phases"] and full["roofline"]["kernel"]["name"].startswith("k_")
+    assert list(full["also"]) == ["Yuma 4 (Rhef+relative bonds) - liquid alpha on"]
+    assert {k: full[k] for k in ("metric", "unit", "dtype", "steps")} == {k: line[k] for k in
+                                                                          ("metric", "unit", "dtype", "steps")}

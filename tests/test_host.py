@@ -547,3 +547,39 @@ def pd_frame(rows):
     import pandas as pd
 
     return pd.DataFrame(rows)
+
+
+def test_bench_dump_outputs_budget_sample_and_determinism(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array lands as <name>.npy in float32 (or
+    float64), whole while it fits its share of the byte budget, else as the
+    seeded sample of its flattened elements the returned record describes;
+    the same arrays give the same files, and nothing but .npy is written."""
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 6 * 1000)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"Dn": torch.rand(5, 1, 8, generator=g), "B_hist": torch.rand(5, 1, 8, 100, generator=g),
+              "table_0": np.arange(12, dtype=np.int64).reshape(3, 4), "C": torch.rand(5, 1, 100, generator=g)}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    again = bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert info == again and set(info) == set(arrays)
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in arrays)
+    total = 0
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "a" / (name + ".npy"))
+        assert np.array_equal(got, np.load(tmp_path / "b" / (name + ".npy")))
+        want = a.numpy() if torch.is_tensor(a) else a
+        assert got.dtype == (np.float32 if want.dtype == np.float32 else np.float64)
+        assert info[name]["shape"] == list(want.shape)
+        total += got.nbytes
+        if not info[name]["sampled"]:
+            assert np.array_equal(got, want)
+            continue
+        rng = np.random.default_rng(info[name]["seed"])
+        idx = np.unique(rng.integers(0, want.size, size=info[name]["draws"], dtype=np.int64))
+        assert info[name]["count"] == idx.size == got.size
+        assert np.array_equal(got, want.reshape(-1)[idx])
+    assert total <= 6 * 1000
+    assert [k for k in arrays if info[k]["sampled"]] == ["B_hist"]  # 16 kB: the only one above its share

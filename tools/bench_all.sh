@@ -1,9 +1,11 @@
 #!/bin/bash
-# One bench line per BASELINE.json config (c2 headline, c3 sweep, c4 wide,
-# c5 sheet) and the other c2 variants on this box; stops at the first failure.
+# One full bench line (bench.py --full) per BASELINE.json config (c2 headline,
+# c3 sweep, c4 wide, c5 sheet) and the other c2 variants on this box; stops at
+# the first failure. Logs under $OUT (default bench_out/).
 #   tools/bench_all.sh [c2 c3 c4 c5 y1 y2 y0]...   (default: all)
 set -u
-mkdir -p gpurun_out
+OUT=${OUT:-bench_out}
+mkdir -p $OUT
 W=${*:-c2 c3 c4 c5 y1 y2 y0}
 for c in $W; do
   case $c in
@@ -15,8 +17,8 @@ for c in $W; do
     y2) extra=(--version "Yuma 2 (Adrian-Fish)" --no-also --steps 5 --warmup 2);;
     y0) extra=(--version "Yuma 0 (subtensor)" --no-also --steps 5 --warmup 2);;
   esac
-  timeout -k 10 400 python bench.py "${extra[@]}" > gpurun_out/bench_$c.log 2>&1
+  timeout -k 10 400 python bench.py --full "${extra[@]}" > $OUT/bench_$c.log 2>&1
   rc=$?
-  echo "$c rc=$rc"; tail -1 gpurun_out/bench_$c.log | cut -c1-400
-  if [ $rc -ne 0 ]; then tail -20 gpurun_out/bench_$c.log; exit $rc; fi
+  echo "$c rc=$rc"; tail -1 $OUT/bench_$c.log | cut -c1-400
+  if [ $rc -ne 0 ]; then tail -20 $OUT/bench_$c.log; exit $rc; fi
 done

@@ -23,9 +23,9 @@ if [[ $WHAT == all || $WHAT == *smoke* ]]; then stage smoke 600 python -c "impor
 if [[ $WHAT == all || $WHAT == *tests* ]]; then
   stage pytest_gpu 1500 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -p no:cacheprovider
 fi
-if [[ $WHAT == all || $WHAT == *bench* ]]; then stage bench 900 python bench.py --steps 5 --warmup 2; fi
+if [[ $WHAT == all || $WHAT == *bench* ]]; then stage bench 900 python bench.py --full --steps 5 --warmup 2; fi
 if [[ $WHAT == all || $WHAT == *prof* ]]; then
-  stage rocprof 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --profile-reps 1
+  stage rocprof 900 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --profile-reps 1
 fi
 if [[ $WHAT == all || $WHAT == *variants* ]]; then
   for v in "Yuma 1 (paper)" "Yuma 2 (Adrian-Fish)" "Yuma 0 (subtensor)"; do
