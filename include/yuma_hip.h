@@ -16,7 +16,8 @@
  *
  * Conventions
  *  - Every pointer argument is DEVICE memory (hipMalloc / torch.cuda tensors),
- *    fp32 row-major, owned by the caller. The engine never allocates, never
+ *    fp32 row-major (W alone may be uint16 row-major: YUMA_RUN_W_U16 below),
+ *    owned by the caller. The engine never allocates, never
  *    synchronises, and is stream-ordered on `stream` (a hipStream_t, NULL =
  *    default stream), so a call can be captured into a hipGraph.
  *  - Layouts: W [E][N][V][M]; S [E][N][V]; B [N][V][M]; per-epoch vectors
@@ -162,12 +163,32 @@ int yuma_run(int variant, const yuma_params_t* params_dev, int N, int E, int V, 
  * over one subnet; SURVEY config c3), so a whole sweep moves one copy of W
  * per epoch through HBM and the scenarios' reads of it meet in the caches.
  * Results are those of yuma_run on W and S replicated per scenario.
- * phase_ms: NULL, or per-phase device time as yuma_run_profiled (blocks).   */
-enum yuma_run_flags { YUMA_RUN_SHARED_INPUTS = 1 };
+ * phase_ms: NULL, or per-phase device time as yuma_run_profiled (blocks).
+ * YUMA_RUN_W_U16 — W addresses uint16_t elements in the same [E][N][V][M]
+ * layout (the on-chain weight format); element w is the weight (float)w, an
+ * exact conversion, so every output has the bits of the same run on the
+ * widened fp32 tensor, for half the device memory and half the bytes per pass
+ * over W. S, params, B_init, Wprev_init, the outputs and the workspace size
+ * keep their meaning. W must be 8-byte aligned (and the fp32 matrices 16-byte
+ * aligned). Accepted by yuma_run_ex and yuma_graph_create_ex where
+ * yuma_u16_native() returns 1; elsewhere they return YUMA_EUNSUPPORTED before
+ * the first launch and the caller widens W itself. Every other entry point
+ * reads fp32 weights only.                                                   */
+enum yuma_run_flags { YUMA_RUN_SHARED_INPUTS = 1, YUMA_RUN_W_U16 = 2 };
 int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                 const float* W, const float* S, const float* B_init, const float* Wprev_init,
                 const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                 int chunk_epochs, int flags, void* stream, float* phase_ms);
+
+/* 1 when yuma_run_ex / yuma_graph_create_ex with these arguments and
+ * YUMA_RUN_W_U16 (`flags`: the run's other flags) read uint16 weights
+ * natively, else 0. Host only, needs no GPU; of `out` it reads only which
+ * pointers are non-NULL (NULL: nothing requested). Native: Yuma 3 and Yuma 4
+ * (scalar or liquid alpha, any reset mode), V <= YUMA_REG_VALIDATORS,
+ * M % 4 == 0, no YUMA_RUN_SHARED_INPUTS, none of Wn / Wc / Wb / B_inst / Tv
+ * requested.                                                                */
+int yuma_u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out,
+                    int flags);
 
 /* hipGraph form of yuma_run: the whole multi-epoch run (every phase of every
  * chunk, no host work between them) captured once into a HIP graph and

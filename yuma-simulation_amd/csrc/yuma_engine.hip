@@ -41,6 +41,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "yuma_hip.h"
@@ -61,6 +62,8 @@ constexpr int kTileM = 64;
 // above, the streaming paths (k_consensus_big, k_rank_sw<BIGV>, ...)
 constexpr int kRegRows = YUMA_REG_VALIDATORS;
 typedef float fvec4 __attribute__((ext_vector_type(4)));       // miner columns per tile: 16 lanes x float4
+// uint16 weights (YUMA_RUN_W_U16): a lane's 4 miner columns are one 8-byte load
+typedef unsigned short usvec4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxTiles = 1 << 20;
 
 // ---------------------------------------------------------------------------
@@ -374,6 +377,53 @@ __device__ __forceinline__ void load4c(const float* __restrict__ base, int row, 
     for (int c = 0; c < 4; ++c) x[c] = NTL ? __builtin_nontemporal_load(r + min(m + c, M - 1)) : r[min(m + c, M - 1)];
   }
 }
+// uint16 weights (the W-reading kernels' WT = uint16_t; M % 4 == 0 and an
+// 8-byte aligned W, so VEC only): the same lane owns the same 4 columns, one
+// 8-byte load instead of 16, converted in registers -- (float)w is exact, so
+// everything downstream sees the bits the fp32 load would have delivered.
+template <bool NTL = false>
+__device__ __forceinline__ usvec4 ldw4(const uint16_t* __restrict__ p) {
+  return NTL ? __builtin_nontemporal_load(reinterpret_cast<const usvec4*>(p))
+             : *reinterpret_cast<const usvec4*>(p);
+}
+template <bool NTL = false>
+__device__ __forceinline__ void ldw4(const uint16_t* __restrict__ p, float (&x)[4]) {
+  const usvec4 t = ldw4<NTL>(p);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) x[c] = (float)t[c];
+}
+template <bool NTL = false>
+__device__ __forceinline__ void ldw4(const float* __restrict__ p, float (&x)[4]) {
+  const fvec4 t = NTL ? __builtin_nontemporal_load(reinterpret_cast<const fvec4*>(p))
+                      : *reinterpret_cast<const fvec4*>(p);
+  x[0] = t.x;
+  x[1] = t.y;
+  x[2] = t.z;
+  x[3] = t.w;
+}
+// load4c of uint16 weights: unconverted (a prefetch ring keeps the loaded
+// quad and converts at the use, so no conversion waits on a load in flight)
+template <bool VEC, bool NTL = false>
+__device__ __forceinline__ void load4c(const uint16_t* __restrict__ base, int row, int V, int m,
+                                       int M, usvec4& x) {
+  static_assert(VEC, "uint16 weights take the vector loads only");
+  const int rr = row < V ? row : V - 1;
+  const int mm = m < M ? m : M - 4;
+  x = ldw4<NTL>(base + (long long)rr * M + mm);
+}
+template <bool VEC, bool NTL = false>
+__device__ __forceinline__ void load4c(const uint16_t* __restrict__ base, int row, int V, int m,
+                                       int M, float (&x)[4]) {
+  usvec4 t;
+  load4c<VEC, NTL>(base, row, V, m, M, t);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) x[c] = (float)t[c];
+}
+// a weight quad as a prefetch ring holds it, and its elements as fp32
+template <typename WT> struct WQuad { typedef float type[4]; };
+template <> struct WQuad<uint16_t> { typedef usvec4 type; };
+__device__ __forceinline__ float wf32(float w) { return w; }
+__device__ __forceinline__ float wf32(unsigned short w) { return (float)w; }
 __device__ __forceinline__ void mask4(int row, int V, int m, int M, float (&x)[4]) {
 #pragma unroll
   for (int c = 0; c < 4; ++c)
@@ -438,8 +488,8 @@ __device__ __forceinline__ float fast_row_rcp(float rs, unsigned bmax, unsigned 
   return ad >= 0x1p-60f && ad <= 0x1p60f && screen_ok(bmax, bmin1) ? 1.0f / rs : qnan();
 }
 
-template <bool VEC, bool WIDE = false>
-__global__ __launch_bounds__(256) void k_rowsum(const float* __restrict__ W,
+template <bool VEC, bool WIDE = false, typename WT = float>
+__global__ __launch_bounds__(256) void k_rowsum(const WT* __restrict__ W,
                                                 const float* __restrict__ S, int V, int M,
                                                 long long islice0, int rowblocks,
                                                 float* __restrict__ rsd, float* __restrict__ sn,
@@ -471,24 +521,20 @@ __global__ __launch_bounds__(256) void k_rowsum(const float* __restrict__ W,
     __shared__ float qs[kMaxWideChunks];
     __shared__ unsigned qb[3][4];
     const int nc = (M + 255) / 256;
-    const float* r = W + (wsl * V + rb) * (long long)M;
+    const WT* r = W + (wsl * V + rb) * (long long)M;
 #pragma unroll 4
     for (int k = wave; k < nc; k += 4) {
       const int m = k * 256 + lane * 4;
       float x[4];
       if (VEC) {
         if (m < M) {
-          const fvec4 t = __builtin_nontemporal_load(reinterpret_cast<const fvec4*>(r + m));
-          x[0] = t.x;
-          x[1] = t.y;
-          x[2] = t.z;
-          x[3] = t.w;
+          ldw4<true>(r + m, x);
         } else {
           x[0] = x[1] = x[2] = x[3] = 0.0f;
         }
       } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = m + c < M ? r[m + c] : 0.0f;
+        for (int c = 0; c < 4; ++c) x[c] = m + c < M ? (float)r[m + c] : 0.0f;
       }
       const float q = wave_sum(((x[0] + x[1]) + x[2]) + x[3]);
       if (lane == 0) qs[k] = q;
@@ -526,7 +572,7 @@ __global__ __launch_bounds__(256) void k_rowsum(const float* __restrict__ W,
   }
   const int row = rb * 4 + wave;
   if (!WIDE && row < V) {
-    const float* r = W + (wsl * V + row) * (long long)M;
+    const WT* r = W + (wsl * V + row) * (long long)M;
     float acc = 0.0f;
 #pragma unroll 4
     for (int m0 = 0; m0 < M; m0 += 256) {
@@ -534,17 +580,13 @@ __global__ __launch_bounds__(256) void k_rowsum(const float* __restrict__ W,
       float x[4];
       if (VEC) {
         if (m < M) {
-          const fvec4 t = __builtin_nontemporal_load(reinterpret_cast<const fvec4*>(r + m));
-          x[0] = t.x;
-          x[1] = t.y;
-          x[2] = t.z;
-          x[3] = t.w;
+          ldw4<true>(r + m, x);
         } else {
           x[0] = x[1] = x[2] = x[3] = 0.0f;
         }
       } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) x[c] = m + c < M ? r[m + c] : 0.0f;
+        for (int c = 0; c < 4; ++c) x[c] = m + c < M ? (float)r[m + c] : 0.0f;
       }
       float q = ((x[0] + x[1]) + x[2]) + x[3];
       q = wave_sum(q);  // the balanced tree over the chunk's 64 quads
@@ -600,8 +642,8 @@ __global__ __launch_bounds__(256) void k_rowsum(const float* __restrict__ W,
 // Per iteration: mid in double exactly as the reference, compared as fp32
 // (torch casts the python scalar), masked stake sums reduced in a fixed tree.
 // ---------------------------------------------------------------------------
-template <int NT, int R, bool VEC>
-__global__ __launch_bounds__(NT) void k_consensus(const float* __restrict__ W,
+template <int NT, int R, bool VEC, typename WT = float>
+__global__ __launch_bounds__(NT) void k_consensus(const WT* __restrict__ W,
                                                   const float* __restrict__ rsd,
                                                   const float* __restrict__ sn,
                                                   const yuma_params_t* __restrict__ prm, int N,
@@ -617,7 +659,7 @@ __global__ __launch_bounds__(NT) void k_consensus(const float* __restrict__ W,
   const int n = (int)(slice % N);
   if (dup_slice(crep, slice, N)) return;  // block-uniform
   const int m = tile * kTileM + L.c4 * 4;
-  const float* Ws = W + in_slice(slice, N, wsh) * (long long)V * M;
+  const WT* Ws = W + in_slice(slice, N, wsh) * (long long)V * M;
 
   float wn[R][4], s[R], d[R];
 #pragma unroll
@@ -1076,8 +1118,8 @@ __device__ __forceinline__ void load_norm_w(const float* __restrict__ Ws, const 
 // min over nonzero |a| taken on 2·bits(|a|) - 1 (zeros wrap to the maximum),
 // instead of three compares per element; no signed-zero fix-up (consensus
 // only compares normalised weights against grid points >= 0).
-template <int R, bool VEC>
-__device__ __forceinline__ void load_norm_w_lds(const float* __restrict__ Ws, const float* rsd_s,
+template <int R, bool VEC, typename WT>
+__device__ __forceinline__ void load_norm_w_lds(const WT* __restrict__ Ws, const float* rsd_s,
                                                 const float* sn_s, float* rl, int V, int M, int m,
                                                 int rg, int lane, float (&wn)[R][4]) {
   constexpr int NR = 16 * R, PL = (NR + 63) / 64;
@@ -1094,11 +1136,15 @@ __device__ __forceinline__ void load_norm_w_lds(const float* __restrict__ Ws, co
     const unsigned o0 = (unsigned)rg * (unsigned)M + (unsigned)m, st = 16u * (unsigned)M;
 #pragma unroll
     for (int i = 0; i < R; ++i) {
-      const float4 t = *reinterpret_cast<const float4*>(Ws + (o0 + (unsigned)i * st));
-      wn[i][0] = t.x;
-      wn[i][1] = t.y;
-      wn[i][2] = t.z;
-      wn[i][3] = t.w;
+      if constexpr (std::is_same_v<WT, float>) {
+        const float4 t = *reinterpret_cast<const float4*>(Ws + (o0 + (unsigned)i * st));
+        wn[i][0] = t.x;
+        wn[i][1] = t.y;
+        wn[i][2] = t.z;
+        wn[i][3] = t.w;
+      } else {
+        ldw4(Ws + (o0 + (unsigned)i * st), wn[i]);
+      }
     }
   } else {
 #pragma unroll
@@ -1448,8 +1494,8 @@ __device__ __forceinline__ void consensus_search(const float (&wn)[R][4], const 
   }
 }
 
-template <int R, bool VEC>
-__global__ __launch_bounds__(256, 4) void k_consensus_w(const float* __restrict__ W,
+template <int R, bool VEC, typename WT = float>
+__global__ __launch_bounds__(256, 4) void k_consensus_w(const WT* __restrict__ W,
                                                      const float* __restrict__ rsd,
                                                      const float* __restrict__ sn,
                                                      const int* __restrict__ sx,
@@ -1596,8 +1642,8 @@ __device__ __forceinline__ int iscan8_excl(int x, int r8) {
 // NP: wave pairs per block (2: a 64-miner tile per 4-wave block; 1: a
 // 32-miner group per 2-wave block, so a block barrier waits for the pair only)
 constexpr int kConsPairs = 2;
-template <bool VEC, int NP = 2>
-__global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const float* __restrict__ W,
+template <bool VEC, int NP = 2, typename WT = float>
+__global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const WT* __restrict__ W,
                                                      const float* __restrict__ rsd,
                                                      const float* __restrict__ sn,
                                                      const int* __restrict__ sx,
@@ -1624,7 +1670,7 @@ __global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const float* __rest
   if (dup_slice(crep, slice, N)) return;  // block-uniform
   const int m = tile * (32 * NP) + pair * 32 + cq * 4;
   const int r0 = h * HR + rg;  // this lane's rows r0 + 8 i
-  const float* Ws = W + in_slice(slice, N, wsh) * (long long)V * M;
+  const WT* Ws = W + in_slice(slice, N, wsh) * (long long)V * M;
   const float* rsd_s = rsd + slice * V;
   const float* sn_s = sn + slice * V;
   float* rw = rl[wave];
@@ -1655,11 +1701,7 @@ __global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const float* __rest
     const unsigned o0 = (unsigned)r0 * (unsigned)M + (unsigned)m, st = 8u * (unsigned)M;
 #pragma unroll
     for (int i = 0; i < R; ++i) {
-      const fvec4 t = __builtin_nontemporal_load(reinterpret_cast<const fvec4*>(Ws + (o0 + (unsigned)i * st)));
-      wn[i][0] = t.x;
-      wn[i][1] = t.y;
-      wn[i][2] = t.z;
-      wn[i][3] = t.w;
+      ldw4<true>(Ws + (o0 + (unsigned)i * st), wn[i]);
     }
   } else {
 #pragma unroll
@@ -2227,8 +2269,8 @@ __global__ __launch_bounds__(256, 1) void k_rank_mc(const float* __restrict__ W,
   }
 }
 
-template <bool VEC, bool YUMA2 = false, bool BCS = false>
-__global__ __launch_bounds__(256, 1) void k_rank_s(const float* __restrict__ W,
+template <bool VEC, bool YUMA2 = false, bool BCS = false, typename WT = float>
+__global__ __launch_bounds__(256, 1) void k_rank_s(const WT* __restrict__ W,
                                                 const float* __restrict__ rsd,
                                                 const float* __restrict__ sn,
                                                 const float* __restrict__ C, int N, int V, int M,
@@ -2258,8 +2300,9 @@ __global__ __launch_bounds__(256, 1) void k_rank_s(const float* __restrict__ W,
   // the clipped matrix and the row sums that normalise it (block-uniform)
   long long wsl = slice;
   bool divide = true;
-  const float* Ws = W + in_slice(slice, N, wsh) * VM;
-  if (YUMA2) {
+  static_assert(!YUMA2 || std::is_same_v<WT, float>, "Yuma2's W_prev is fp32");
+  const WT* Ws = W + in_slice(slice, N, wsh) * VM;
+  if constexpr (YUMA2) {
     if (slice >= N) {
       wsl = slice - N;
       Ws = W + in_slice(wsl, N, wsh) * VM;
@@ -2404,8 +2447,8 @@ __global__ __launch_bounds__(256, 1) void k_rank_s(const float* __restrict__ W,
 // BIGV (above kRegRows validators): the row sums, reciprocals and stakes are
 // read per row from memory instead of the LDS staging.
 constexpr int kRankWide = 1;  // launch the wide form (0: k_rank_s everywhere)
-template <bool VEC, bool YUMA2 = false, bool BCS = false, bool BIGV = false>
-__global__ __launch_bounds__(256, 1) void k_rank_sw(const float* __restrict__ W,
+template <bool VEC, bool YUMA2 = false, bool BCS = false, bool BIGV = false, typename WT = float>
+__global__ __launch_bounds__(256, 1) void k_rank_sw(const WT* __restrict__ W,
                                                  const float* __restrict__ rsd,
                                                  const float* __restrict__ sn,
                                                  const float* __restrict__ C, int N, int V, int M,
@@ -2436,8 +2479,9 @@ __global__ __launch_bounds__(256, 1) void k_rank_sw(const float* __restrict__ W,
   const int m = cb * CB + lane * 4;
   long long wsl = slice;
   bool divide = true;
-  const float* Ws = W + in_slice(slice, N, wsh) * VM;
-  if (YUMA2) {
+  static_assert(!YUMA2 || std::is_same_v<WT, float>, "Yuma2's W_prev is fp32");
+  const WT* Ws = W + in_slice(slice, N, wsh) * VM;
+  if constexpr (YUMA2) {
     if (slice >= N) {
       wsl = slice - N;
       Ws = W + in_slice(wsl, N, wsh) * VM;
@@ -3167,7 +3211,7 @@ __global__ __launch_bounds__(256) void k_incentive(float* __restrict__ Rio,
 // dpart[slice][tile][v] = sum over the tile's columns of B_state * I.
 // ---------------------------------------------------------------------------
 struct BondArgs {
-  const float* W;
+  const float* W;  // k_bonds_elem<.., WT = uint16_t>: uint16 elements behind this pointer
   const float* rsd;
   const float* sn;
   const float* C;
@@ -4005,7 +4049,7 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // 4 rows x 256 B (CB = 64) or 1 row x 1 KiB (CB >= 256). The dividend partial
 // of each 64-miner tile is the 16-lane DPP sum of one DPP row in every shape.
 template <int VARIANT, int R, bool VEC, int P, bool VECI, bool NT = false, int BS = 256, int CB = 64,
-          int DPL = DP_TV, bool RQ = false>
+          int DPL = DP_TV, bool RQ = false, typename WT = float>
 __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
   constexpr int LPR = CB / 4, G = BS / LPR;
   static_assert(CB % 64 == 0 && BS % LPR == 0, "a 16-lane DPP row must cover one 64-miner tile");
@@ -4030,6 +4074,8 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
   constexpr bool COLNORM = VARIANT == YUMA_VARIANT_YUMA1 || VARIANT == YUMA_VARIANT_YUMA2;
   constexpr bool YUMA2 = VARIANT == YUMA_VARIANT_YUMA2;
   static_assert(VARIANT != YUMA_VARIANT_RUST, "YumaRust renormalises B_ema over every validator (k_bonds_cn)");
+  static_assert(!COLNORM || std::is_same_v<WT, float>, "uint16 weights: Yuma 3 / Yuma 4 only");
+  const WT* const Wa = reinterpret_cast<const WT*>(A.W);  // BondArgs::W in the launch's element type
   const int row0 = rb * G * R + g;
   // the conditional reset's test (C of the previous epoch at the reset
   // column), read before the epoch loop: a load in the loop's rare reset
@@ -4088,7 +4134,8 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
     }
   }
 
-  float rw[P][R][4], rd[P][R], rsn[P][R], ri[P][4], rba[P][4];
+  typename WQuad<WT>::type rw[P][R];  // fp32: float [P][R][4]; uint16: the quads as loaded
+  float rd[P][R], rsn[P][R], ri[P][4], rba[P][4];
   float rcc[COLNORM ? P : 1][4], rcs[COLNORM ? P : 1][4], rcr[COLNORM ? P : 1][4];  // Yuma / Yuma2: C, csb, csr
   float rrq[RQ ? P : 1][RQ ? R : 1];  // RQ: k_rowsum's screened RN(1 / row sum) (rq4.y)
   // DP_QTE: the quad partials of up to kQBuf epochs parked in LDS (one float
@@ -4111,7 +4158,7 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
       // the one-row history-less scan streams each W slice exactly once
       // (rowsum / consensus / rank read it in their own launches): non-
       // temporal loads (c4 bonds 1.63 -> 1.50 ms, same box)
-      load4c<VEC, DPL == DP_QTE>(A.W + (A.wsh ? (long long)t : slice) * VM, rr, V, m, M, rw[k][i]);
+      load4c<VEC, DPL == DP_QTE>(Wa + (A.wsh ? (long long)t : slice) * VM, rr, V, m, M, rw[k][i]);
       rd[k][i] = A.rsd[slice * V + rr];
       rsn[k][i] = A.sn[slice * V + rr];
       // RQ: the screened reciprocal alone (rq4.y). (One 16-byte rq4 load for
@@ -4204,7 +4251,7 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
           // screen (NaN reciprocal) sends the wave to IEEE division
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
-            const float a = rw[k][i][c];
+            const float a = wf32(rw[k][i][c]);
             const float q = a * rrq[k][i];
             const float e = fmaf(-rd[k][i], q, a);
             const float q1 = fmaf(e, rrq[k][i], q);
@@ -4212,17 +4259,17 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
           }
           if (__any(rrq[k][i] != rrq[k][i])) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) wn[c] = rw[k][i][c] / rd[k][i];
+            for (int c = 0; c < 4; ++c) wn[c] = wf32(rw[k][i][c]) / rd[k][i];
           }
         } else {
           const RowDiv rdv = row_div(rd[k][i]);
           bool slow = false;
 #pragma unroll
           for (int c = 0; c < 4; ++c)
-            wn[c] = SHORT ? div_fast_nz(rw[k][i][c], rdv, slow) : div_fast(rw[k][i][c], rdv, slow);
+            wn[c] = SHORT ? div_fast_nz(wf32(rw[k][i][c]), rdv, slow) : div_fast(wf32(rw[k][i][c]), rdv, slow);
           if (__any(slow)) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) wn[c] = rw[k][i][c] / rd[k][i];
+            for (int c = 0; c < 4; ++c) wn[c] = wf32(rw[k][i][c]) / rd[k][i];
           }
         }
         if constexpr (COLNORM) {
@@ -5226,12 +5273,12 @@ RowCfg row_cfg(int V) {
 #define YK_LAUNCH(kernel, grid, block, stream, ...) \
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (hipStream_t)(stream), __VA_ARGS__)
 
-template <int R, bool VEC>
-void launch_consensus_w(long long nblocks, hipStream_t st, const float* W, const float* rsd,
+template <int R, bool VEC, typename WT>
+void launch_consensus_w(long long nblocks, hipStream_t st, const WT* W, const float* rsd,
                         const float* sn, const int* sx, const yuma_params_t* prm, int N, int V,
                         int M, long long slice0, int tiles, double* craw, float* P, int wsh,
                         const int* crep) {
-  YK_LAUNCH((yk::k_consensus_w<R, VEC>), nblocks, 256, st, W, rsd, sn, sx, prm, N, V, M, slice0,
+  YK_LAUNCH((yk::k_consensus_w<R, VEC, WT>), nblocks, 256, st, W, rsd, sn, sx, prm, N, V, M, slice0,
             tiles, craw, P, wsh, crep);
 }
 
@@ -5255,15 +5302,19 @@ void launch_consensus_mc(RowCfg rc, long long nblocks, hipStream_t st, const flo
   }
 }
 
-template <bool VEC>
-void launch_consensus(RowCfg rc, long long nblocks, hipStream_t st, const float* W,
+// WT: the weight element type. uint16 weights (yuma_u16_native) reach only the
+// register-resident kernels of this tree; the rest stay fp32 instantiations.
+template <bool VEC, typename WT>
+void launch_consensus(RowCfg rc, long long nblocks, hipStream_t st, const WT* W,
                       const float* rsd, const float* sn, const int* sx,
                       const yuma_params_t* prm, int N, int V, int M, long long slice0, int tiles,
                       double* craw, float* P, int wsh, const int* crep,
                       const float4* rq4 = nullptr) {
+  constexpr bool F32 = std::is_same_v<WT, float>;
   if (V > yk::kRegRows) {  // the column streamed per search pass
-    YK_LAUNCH(yk::k_consensus_big<VEC>, nblocks, 256, st, W, rsd, sn, prm, N, V, M, slice0, tiles, craw, P,
-              wsh, crep);
+    if constexpr (F32)
+      YK_LAUNCH(yk::k_consensus_big<VEC>, nblocks, 256, st, W, rsd, sn, prm, N, V, M, slice0, tiles, craw, P,
+                wsh, crep);
     return;
   }
   switch (rc) {  // wave-owned columns up to 256 validators
@@ -5288,7 +5339,7 @@ void launch_consensus(RowCfg rc, long long nblocks, hipStream_t st, const float*
       if (VEC && !wsh && P == nullptr) {
         constexpr int NP = yk::kConsPairs;
         const long long nb = NP == 2 ? nblocks : nblocks / tiles * ((M + 31) / 32);
-        YK_LAUNCH((yk::k_consensus_p<true, NP>), nb, 128 * NP, st, W, rsd, sn, sx, prm, N, V, M, slice0, tiles,
+        YK_LAUNCH((yk::k_consensus_p<true, NP, WT>), nb, 128 * NP, st, W, rsd, sn, sx, prm, N, V, M, slice0, tiles,
                   craw, P, wsh, crep, rq4);
       }
       else
@@ -5300,19 +5351,22 @@ void launch_consensus(RowCfg rc, long long nblocks, hipStream_t st, const float*
   }
   switch (rc) {
     case RC_256_1:
-      YK_LAUNCH((yk::k_consensus<256, 1, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
-                slice0, tiles, craw, P, wsh, crep);
+      if constexpr (F32)
+        YK_LAUNCH((yk::k_consensus<256, 1, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
+                  slice0, tiles, craw, P, wsh, crep);
       break;
     case RC_256_4:
-      YK_LAUNCH((yk::k_consensus<256, 4, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
-                slice0, tiles, craw, P, wsh, crep);
+      if constexpr (F32)
+        YK_LAUNCH((yk::k_consensus<256, 4, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
+                  slice0, tiles, craw, P, wsh, crep);
       break;
     case RC_256_16:
-      YK_LAUNCH((yk::k_consensus<256, 16, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
-                slice0, tiles, craw, P, wsh, crep);
+      if constexpr (F32)
+        YK_LAUNCH((yk::k_consensus<256, 16, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
+                  slice0, tiles, craw, P, wsh, crep);
       break;
     case RC_1024_16:
-      YK_LAUNCH((yk::k_consensus<1024, 16, VEC>), nblocks, 1024, st, W, rsd, sn, prm, N, V, M,
+      YK_LAUNCH((yk::k_consensus<1024, 16, VEC, WT>), nblocks, 1024, st, W, rsd, sn, prm, N, V, M,
                 slice0, tiles, craw, P, wsh, crep);
       break;
   }
@@ -5435,6 +5489,24 @@ void launch_rank(RowCfg rc, long long nblocks, hipStream_t st, const float* W, c
   }
 }
 
+// uint16 weights (yuma_u16_native: Yuma 3 / Yuma 4, <= kRegRows validators, no
+// materialised matrices, no shared inputs): of the tree above only the plain
+// streaming ranks are reachable -- the wide form for wide subnets, else
+// k_rank_s -- chosen by the same test.
+template <bool VEC>
+void launch_rank(RowCfg, long long nblocks, hipStream_t st, const uint16_t* W, const float* rsd,
+                 const float* sn, const float* C, int N, int V, int M, long long slice0, int tiles,
+                 float* R, float* rpart) {
+  if (M >= 16384 && yk::kRankWide) {
+    const long long nb = nblocks / tiles * ((M + 255) / 256);
+    YK_LAUNCH((yk::k_rank_sw<VEC, false, false, false, uint16_t>), nb, 256, st, W, rsd, sn, C, N, V, M,
+              slice0, tiles, R, rpart, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    return;
+  }
+  YK_LAUNCH((yk::k_rank_s<VEC, false, false, uint16_t>), nblocks, 256, st, W, rsd, sn, C, N, V, M, slice0,
+            tiles, R, rpart, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
 // Column-normalised variants (Rust / Yuma1 / Yuma2): one block owns whole
 // columns (single row block). Run outputs of subnets above 64 validators take
 // the strip scan k_bonds_cn (16-miner strips, 8 waves, epochs in flight);
@@ -5465,7 +5537,7 @@ int launch_cn_rows(hipStream_t st, yk::BondArgs& A, int* ptiles) {
   if (V <= 512) return launch_cn<VARIANT, 4>(st, A, ptiles);
   return launch_cn<VARIANT, 8>(st, A, ptiles);
 }
-template <int VARIANT, bool VEC>
+template <int VARIANT, bool VEC, typename WT = float>
 int launch_bonds_elem(hipStream_t st, yk::BondArgs& A);
 template <int VARIANT, bool VEC>
 int launch_bonds_colnorm(RowCfg rc, hipStream_t st, yk::BondArgs& A, int* ptiles) {
@@ -5542,28 +5614,31 @@ constexpr int kScanGroup = 4;  // scenarios per block of the shared-input scan
 // 0.985-0.997 -> 0.916-0.923; profiles/r05/ab_elem_rq.txt)
 constexpr bool kElemRq(int variant, bool hist) { return hist ? variant <= YUMA_VARIANT_YUMA2 : true; }
 int bonds_rows(bool vec, bool hist, bool wsh) { return vec && (hist || wsh) ? 2 : 1; }
-template <int VARIANT, int R, bool VEC, int P, bool VECI, bool NT, int BS, int CB, int DPL, bool RQ = false>
+template <typename WT, int VARIANT, int R, bool VEC, int P, bool VECI, bool NT, int BS, int CB, int DPL,
+          bool RQ = false>
 int launch_elem_shape(hipStream_t st, yk::BondArgs& A) {
   constexpr int G = BS / (CB / 4);
   A.rowblocks = (A.V + G * R - 1) / (G * R);
   A.cblocks = (A.M + CB - 1) / CB;
   const long long nblocks = (long long)A.N * A.rowblocks * A.cblocks;
-  YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ>), nblocks, BS, st, A);
+  YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT>), nblocks, BS, st, A);
   return DPL;
 }
-template <int VARIANT, bool VEC>
+// WT: the element type A.W addresses (uint16 weights: Yuma 3 / Yuma 4, never
+// the shared-input sweep scan)
+template <int VARIANT, bool VEC, typename WT>
 int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
   const bool hist = A.B_hist != nullptr;
   if constexpr (VEC) {
     if (hist && A.M >= 1024) {
       constexpr int P = VARIANT <= YUMA_VARIANT_YUMA2 ? kWidePCn : kWideP;
       if constexpr (kElemRq(VARIANT, true)) {
-        if (A.rq4 != nullptr) return launch_elem_shape<VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, true>(st, A);
+        if (A.rq4 != nullptr) return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, true>(st, A);
       }
-      return launch_elem_shape<VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ>(st, A);
+      return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ>(st, A);
     }
   }
-  if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3) {
+  if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float>) {
     if (A.wsh && A.N >= 2 && A.rq4 != nullptr) {  // a sweep over one input trajectory
       constexpr int K = kScanGroup, R = 2;
       A.rowblocks = (A.V + 16 * R - 1) / (16 * R);
@@ -5584,16 +5659,16 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
     if constexpr (VEC && kElemRq(VARIANT, false)) {
       if (A.rq4 != nullptr) {
         if (blocks_r2 >= 4096)
-          return launch_elem_shape<VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, true>(st, A);
-        return launch_elem_shape<VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, true>(st, A);
+          return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, true>(st, A);
+        return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, true>(st, A);
       }
     }
     if (blocks_r2 >= 4096)
-      return launch_elem_shape<VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE>(st, A);
-    return launch_elem_shape<VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE>(st, A);
+      return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE>(st, A);
+    return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE>(st, A);
   }
-  if (hist) return launch_elem_shape<VARIANT, 2, VEC, 2, VEC, true, 256, 64, yk::DP_TV>(st, A);
-  return launch_elem_shape<VARIANT, 2, VEC, 2, VEC, false, 256, 64, yk::DP_TV>(st, A);
+  if (hist) return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, true, 256, 64, yk::DP_TV>(st, A);
+  return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, false, 256, 64, yk::DP_TV>(st, A);
 }
 
 // Launch the bond scan for A.N scenarios over epochs [A.t0, A.t1); returns
@@ -5637,10 +5712,27 @@ struct PhaseTimer {
   }
 };
 
-int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, const float* W,
+// Whether a run with these arguments and YUMA_RUN_W_U16 reads its uint16
+// weights natively (yuma_u16_native): the element-wise variants on the
+// register-resident, streaming kernels. Only these are instantiated for
+// uint16_t; everything else is served by widening W to fp32 first.
+bool u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || V < 1 || M < 1 || V > YUMA_REG_VALIDATORS || (M % 4) != 0) return false;
+  if (flags & YUMA_RUN_SHARED_INPUTS) return false;
+  if (out != nullptr && (out->Wn || out->Wc || out->Wb || out->B_inst || out->Tv)) return false;
+  return true;
+}
+
+// WT: the element type of W, float or (YUMA_RUN_W_U16) uint16_t. Element w of
+// a uint16 W is the weight (float)w; slices and rows are indexed in elements.
+template <typename WT>
+int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, const WT* W,
              const float* S, const float* B_init, const float* Wprev_init,
              const yuma_outputs_t* out, void* workspace, size_t ws_bytes, int chunk,
              void* stream, float* phase_ms = nullptr, int wsh = 0) {
+  constexpr bool U16 = std::is_same_v<WT, uint16_t>;
+  static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
   if (variant < 0 || variant > 4) return fail(YUMA_EINVAL, "unknown variant %d", variant);
   if (N < 1 || E < 1 || V < 1 || M < 1)
     return fail(YUMA_EINVAL, "sizes must be positive (N=%d E=%d V=%d M=%d)", N, E, V, M);
@@ -5661,11 +5753,22 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
   const int tiles = (M + yk::kTileM - 1) / yk::kTileM;
   const RowCfg rc = row_cfg(V);
 
-  bool vec = (M % 4) == 0 && aligned16(W);
+  // a lane's 4 columns are one vector load: 16 bytes of fp32, 8 of uint16
+  bool vec = (M % 4) == 0 && ((uintptr_t)W & (4 * sizeof(WT) - 1)) == 0;
   const float* mats[] = {B_init, Wprev_init, out->Wn, out->Wc, out->Wb, out->B_inst,
                          out->B_hist, out->B_final};
   for (const float* p : mats)
     if (p != nullptr && !aligned16(p)) vec = false;
+  if constexpr (U16) {  // before the first launch
+    if (!u16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
+      return fail(YUMA_EUNSUPPORTED,
+                  "YUMA_RUN_W_U16 is not native for variant=%d V=%d M=%d shared=%d or the requested "
+                  "outputs (yuma_u16_native): widen W to fp32",
+                  variant, V, M, wsh);
+    if (!vec)
+      return fail(YUMA_EUNSUPPORTED,
+                  "YUMA_RUN_W_U16 needs W 8-byte aligned and the fp32 matrices 16-byte aligned");
+  }
 
   float* C = out->C ? out->C : ws.C;
   float* I = out->I ? out->I : ws.I;
@@ -5724,7 +5827,14 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
       const int nchunks = (M + 255) / 256;
       const bool wide = nchunks >= yk::kWideChunks && nchunks <= yk::kMaxWideChunks;
       tm.mark(YUMA_PHASE_ROWSUM);
-      if (wide && vec)
+      if constexpr (U16) {  // vec holds
+        if (wide)
+          YK_LAUNCH((yk::k_rowsum<true, true, WT>), rs_in * V, 256, st, W, S, V, M, rs_s0, V, ws.rsd,
+                    ws.sn, 0, ws.sx, fan, ws.rq4);
+        else
+          YK_LAUNCH((yk::k_rowsum<true, false, WT>), rs_in * rowblocks4, 256, st, W, S, V, M, rs_s0,
+                    rowblocks4, ws.rsd, ws.sn, 0, ws.sx, fan, ws.rq4);
+      } else if (wide && vec)
         YK_LAUNCH((yk::k_rowsum<true, true>), rs_in * V, 256, st, W, S, V, M, rs_s0, V, ws.rsd,
                   ws.sn, 0, ws.sx, fan, ws.rq4);
       else if (wide)
@@ -5737,7 +5847,10 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
         YK_LAUNCH(yk::k_rowsum<false>, rs_in * rowblocks4, 256, st, W, S, V, M, rs_s0,
                   rowblocks4, ws.rsd, ws.sn, 0, ws.sx, fan, ws.rq4);
       tm.mark(YUMA_PHASE_CONSENSUS);
-      if (mc) {
+      if constexpr (U16) {
+        launch_consensus<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, s0, tiles,
+                               ws.craw, out->P, wsh, crep, ws.rq4);
+      } else if (mc) {
         const int G = N < yk::kMcGroups ? N : yk::kMcGroups;
         const long long nb = (long long)(c1 - c0) * tiles * G;
         if (vec)
@@ -5760,7 +5873,9 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
       // rank classes are those classes (no bond column sums) and the streaming
       // rank of <= 1024 validators on 64-miner tiles would run
       const int* rlist = (mc && rcrep == crep && csb == nullptr && M < 16384) ? ws.clist : nullptr;
-      if (vec)
+      if constexpr (U16)
+        launch_rank<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, N, V, M, s0, tiles, Rr, ws.rpart);
+      else if (vec)
         launch_rank<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
                           variant == YUMA_VARIANT_YUMA2, N, V, M, s0, tiles, Rr, ws.rpart, out->Wn,
                           out->Wc, ws.tvc, ws.tvn, wsh, rcrep, csb, ws.csr, prm, rlist);
@@ -5776,7 +5891,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
               (out->R != nullptr || variant == YUMA_VARIANT_RUST) ? 1 : 0);
 
     yk::BondArgs A{};
-    A.W = W;
+    A.W = reinterpret_cast<const float*>(W);  // the scan is launched for WT
     A.rsd = ws.rsd;
     A.sn = ws.sn;
     A.C = C;
@@ -5806,8 +5921,13 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
     A.ep = dte_stride(E);
     tm.mark(YUMA_PHASE_BONDS);
     int ptiles = tiles;
-    int dpl = vec ? launch_bonds<true>(variant, rc, st, A, &ptiles)
-                  : launch_bonds<false>(variant, rc, st, A, &ptiles);
+    int dpl;
+    if constexpr (U16)
+      dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem<YUMA_VARIANT_YUMA3, true, WT>(st, A)
+                                          : launch_bonds_elem<YUMA_VARIANT_YUMA4, true, WT>(st, A);
+    else
+      dpl = vec ? launch_bonds<true>(variant, rc, st, A, &ptiles)
+                : launch_bonds<false>(variant, rc, st, A, &ptiles);
     tm.mark(YUMA_PHASE_FINALIZE);
     const float* dsrc = ws.dpart;
     if (dpl == yk::DP_QTE) {
@@ -6018,6 +6138,8 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
 
 }  // namespace
 
+constexpr int kRunFlags = YUMA_RUN_SHARED_INPUTS | YUMA_RUN_W_U16;
+
 struct yuma_graph {
   hipGraph_t graph;
   hipGraphExec_t exec;
@@ -6042,10 +6164,17 @@ int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int 
                 const float* W, const float* S, const float* B_init, const float* Wprev_init,
                 const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                 int chunk_epochs, int flags, void* stream, float* phase_ms) {
-  if (flags & ~YUMA_RUN_SHARED_INPUTS) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
+  if (flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
+  const int wsh = (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
+  if (flags & YUMA_RUN_W_U16)
+    return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
+                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh);
   return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream, phase_ms,
-                  (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0);
+                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh);
+}
+
+int yuma_u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  return u16_native(variant, N, E, V, M, out, flags) ? 1 : 0;
 }
 
 int yuma_run_profiled(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
@@ -6091,9 +6220,13 @@ int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* 
                          int E, int V, int M, const float* W, const float* S,
                          const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                          void* workspace, size_t workspace_bytes, int chunk_epochs, int flags) {
-  if (flags & ~YUMA_RUN_SHARED_INPUTS) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
+  if (flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
   if (graph == nullptr) return fail(YUMA_EINVAL, "graph handle pointer is NULL");
   *graph = nullptr;
+  const int wsh = (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
+  // refused before the capture starts (run_impl would refuse it before its first launch)
+  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags))
+    return fail(YUMA_EUNSUPPORTED, "YUMA_RUN_W_U16 is not native for these arguments (yuma_u16_native)");
   hipStream_t cs = nullptr;
   if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess)
     return fail(YUMA_EHIP, "capture stream creation failed");
@@ -6101,9 +6234,12 @@ int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* 
     (void)hipStreamDestroy(cs);
     return fail(YUMA_EHIP, "hipStreamBeginCapture failed");
   }
-  const int rc = run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out,
-                          workspace, workspace_bytes, chunk_epochs, cs, nullptr,
-                          (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0);
+  const int rc = (flags & YUMA_RUN_W_U16)
+                     ? run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S,
+                                B_init, Wprev_init, out, workspace, workspace_bytes, chunk_epochs, cs,
+                                nullptr, wsh)
+                     : run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                                workspace_bytes, chunk_epochs, cs, nullptr, wsh);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(cs, &g);
   (void)hipStreamDestroy(cs);

@@ -35,6 +35,7 @@ FLAG_NO_HIST = 1  # yuma_params_t.flags: plain bisection instead of the histogra
 FLAG_RESET_ALL_COLUMNS = 2  # the reset zeroes every column (reset_bonds_index None)
 RESET_NONE, RESET_ALWAYS, RESET_IF_ZERO_CONSENSUS = range(3)
 RUN_SHARED_INPUTS = 1  # yuma_run_ex flags
+RUN_W_U16 = 2  # ... W holds uint16 elements (the on-chain weight format), read natively
 LIQUID_OFF, LIQUID_QUANTILE, LIQUID_CONST_AB = range(3)
 OVR_HIGH, OVR_LOW, OVR_FORCE_Q99 = 1, 2, 4
 
@@ -161,6 +162,10 @@ def load_library(path: str | None = None):
         lib.yuma_run_profiled.restype = i32
         lib.yuma_run_ex.argtypes = lib.yuma_run.argtypes[:-1] + [i32, vp, ctypes.POINTER(ctypes.c_float)]
         lib.yuma_run_ex.restype = i32
+        # (not in EXPORTED_SYMBOLS: that tuple mirrors the header scan of
+        # test_host.py, whose pattern takes lower-case letters only)
+        lib.yuma_u16_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
+        lib.yuma_u16_native.restype = i32
         lib.yuma_epoch.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
         lib.yuma_epoch.restype = i32
         lib.yuma_shard_stage.argtypes = [i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
@@ -431,6 +436,45 @@ def _as_dev(x: torch.Tensor, dev) -> torch.Tensor:
     return x.to(device=dev, dtype=torch.float32).contiguous()
 
 
+_MATRIX_OUTPUTS = ("Wn", "Wc", "Wb", "B_inst", "Tv")  # what the uint16 path does not produce
+
+
+def u16_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False,
+               want: tuple[str, ...] = (), *, shared_inputs: bool = False) -> bool:
+    """Whether `run` on a torch.uint16 W with these arguments reads the 16-bit
+    weights natively (yuma_u16_native; needs the library, not a GPU): Yuma 3 /
+    Yuma 4, V <= 1024, M % 4 == 0, no shared inputs, none of Wn / Wc / Wb /
+    B_inst / Tv wanted. Otherwise `run` widens W to fp32 on the device."""
+    names = {"Dn", "C", "I", "B_final", *want}
+    if want_hist:
+        names.add("B_hist")
+    outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
+    flags = RUN_SHARED_INPUTS if shared_inputs else 0
+    return bool(load_library().yuma_u16_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
+
+
+def to_u16(W: torch.Tensor) -> torch.Tensor:
+    """The on-chain max-upscale of float weights to 16 bits: per row (last
+    dimension) round_half_even(w / rowmax * 65535), computed in float64; an
+    all-zero row stays zero. Negative, NaN or infinite entries raise
+    ValueError. Returns torch.uint16 of the same shape.
+
+    This CHANGES the weights: a row is rescaled and every entry rounded to one
+    of 65536 levels, so a run on the result differs from a run on the float
+    input (the normalised weights move by up to 2^-17 relative to the row
+    maximum). It is the format conversion the chain applies, not a
+    parity-preserving one; only a tensor that already holds integers in
+    [0, 65535] with 65535 in every nonzero row maps to itself."""
+    w = torch.as_tensor(W).detach().to(device="cpu", dtype=torch.float64)
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+        raise ValueError("to_u16 takes finite, non-negative weights")
+    mx = w.amax(dim=-1, keepdim=True)
+    # (w * 65535) / rowmax: the product is exact for 16-bit inputs, so a true
+    # tie reaches the rounding as a tie; an all-zero row divides by 1
+    q = w * 65535.0 / torch.where(mx > 0, mx, torch.ones_like(mx))
+    return torch.from_numpy(np.rint(q.numpy()).astype(np.uint16))  # rint: half to even
+
+
 def workspace_bytes(variant: int, N: int, E: int, V: int, M: int, full: bool) -> int:
     return int(load_library().yuma_workspace_bytes(variant, N, E, V, M, 1 if full else 0))
 
@@ -465,7 +509,16 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         N = Nw
         if len(params) != N:
             raise ValueError("one parameter record per scenario is required")
-    W = _as_dev(W, dev)
+    # uint16 weights stay 16-bit on the device where the engine reads them
+    # natively (u16_native); anywhere else they are widened like any dtype
+    w_u16 = False
+    if W.dtype == torch.uint16:
+        W = W.to(device=dev).contiguous()
+        names = tuple(want) + tuple(k for k, v in (out or {}).items() if v is not None)
+        w_u16 = (not single_call and W.data_ptr() % 8 == 0
+                 and u16_native(variant, N, E, V, M, want_hist, names, shared_inputs=shared_inputs))
+    if not w_u16:
+        W = _as_dev(W, dev)
     S = _as_dev(S, dev)
     B_init = None if B_init is None else _as_dev(B_init, dev)
     Wprev_init = None if Wprev_init is None else _as_dev(Wprev_init, dev)
@@ -500,7 +553,26 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     args = (variant, prm.data_ptr(), N, E, V, M, W.data_ptr(), S.data_ptr(),
             _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
             workspace.data_ptr(), workspace.numel(), int(chunk_epochs), stream)
-    if single_call:  # one Yuma* call per slice: the yuma_epoch entry point
+    if w_u16:
+        # the fp32 matrices of the vector paths: a view at an odd offset sends
+        # the fp32 run to its scalar loads, which the uint16 kernels lack
+        mats = [B_init, Wprev_init] + [o.get(k) for k in ("B_hist", "B_final")]
+        if any(t is not None and t.data_ptr() % 16 for t in mats):
+            w_u16 = False
+            W = _as_dev(W, dev)
+            args = args[:6] + (W.data_ptr(),) + args[7:]
+    if w_u16:  # yuma_run_ex / yuma_graph_create_ex with YUMA_RUN_W_U16
+        if capture is not None:
+            h = ctypes.c_void_p()
+            torch.cuda.synchronize(dev)
+            _check(lib.yuma_graph_create_ex(ctypes.byref(h), *args[:-1], RUN_W_U16), "yuma_graph_create_ex")
+            capture.append(h)
+        else:
+            buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
+            _check(lib.yuma_run_ex(*args[:-1], RUN_W_U16, stream, buf), "yuma_run_ex")
+            if phase_ms is not None:
+                phase_ms[:] = list(buf)
+    elif single_call:  # one Yuma* call per slice: the yuma_epoch entry point
         if E != 1 or capture is not None or phase_ms is not None:
             raise ValueError("single_call is one epoch, launched directly")
         _check(lib.yuma_epoch(variant, prm.data_ptr(), N, V, M, W.data_ptr(), _ptr(Wprev_init),
@@ -529,6 +601,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
+    keep["w_path"] = "u16" if w_u16 else "f32"  # how W was read: natively as uint16, or as fp32
     return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], o.get("B_hist"), keep)
 
 
