@@ -331,20 +331,29 @@ def state_key(variant: str) -> str:
 
 
 def run(version: str, W_epochs, S_epochs, cfg, reset_epoch=None, reset_index=None,
-        validators=None):
+        validators=None, B_init=None, W_prev_init=None, return_weight=False):
     """The epoch loop of run_simulation (simulation_utils.py:26-112).
     Returns dict with per-epoch arrays Dn [E,V], C [E,M], I [E,M], B [E,V,M]
-    and, if `validators` is given, the dividends-per-1000-tao lists."""
+    and, if `validators` is given, the dividends-per-1000-tao lists.
+
+    `B_init` [V,M] / `W_prev_init` [V,M] (Yuma 2's previous normalised
+    weights) seed the loop's state before epoch 0, so a run can resume from
+    another run's last epoch. The reset rule is the loop's own: an "always"
+    reset at epoch 0 fires on a given state, a conditional one cannot (there
+    is no previous consensus yet). `return_weight` adds Wn [E,V,M], the
+    normalised weights of every epoch."""
     if version not in VERSIONS:
         raise ValueError("Invalid Yuma function.")
     variant, reset = VERSIONS[version]
     W_epochs = np.asarray(W_epochs, F32)
     S_epochs = np.asarray(S_epochs, F32)
     E = W_epochs.shape[0]
-    B_state = None
+    B_state = None if B_init is None else np.array(B_init, dtype=F32)
     W_prev = None
+    if W_prev_init is not None and variant == YUMA2:
+        W_prev = np.array(W_prev_init, dtype=F32)
     C_prev = None
-    Dn, Cs, Is, Bs = [], [], [], []
+    Dn, Cs, Is, Bs, Wns = [], [], [], [], []
     for epoch_i in range(E):
         if B_state is not None and epoch_i == reset_epoch and reset is not None:
             fire = reset == "always" or (C_prev is not None and C_prev[reset_index] == 0.0)
@@ -360,7 +369,11 @@ def run(version: str, W_epochs, S_epochs, cfg, reset_epoch=None, reset_index=Non
         Cs.append(C_prev)
         Is.append(res["server_incentive"])
         Bs.append(np.array(B_state, copy=True))
+        if return_weight:
+            Wns.append(res["weight"])
     out = {"Dn": np.stack(Dn), "C": np.stack(Cs), "I": np.stack(Is), "B": np.stack(Bs)}
+    if return_weight:
+        out["Wn"] = np.stack(Wns)
     if validators is not None:
         out["dividends"] = dividends_per_1000_tao(validators, S_epochs, out["Dn"], cfg)
     return out

@@ -162,6 +162,24 @@ def test_reset_index_follows_python_indexing():
                            reset_epoch=3, reset_index=-1)
 
 
+def test_reset_at_epoch_zero_of_a_resumed_run():
+    """make_params(resumed=True): the run is given a B_init, so the reset
+    statement is reached at epoch 0 too; without it (the default) an epoch-0
+    reset is dropped as before. The cached form keys on the flag."""
+    mk = lambda f, mode, e, **kw: f(engine.VARIANT_YUMA3, Y.YumaConfig(), reset_mode=mode, reset_epoch=e,
+                                    reset_index=5, n_miners=12, n_epochs=8, **kw)
+    for f in (engine.make_params, engine.make_params_cached):
+        p = mk(f, engine.RESET_ALWAYS, 0, resumed=True)
+        assert (p.reset_mode, p.reset_epoch, p.reset_index) == (engine.RESET_ALWAYS, 0, 5)
+        assert mk(f, engine.RESET_ALWAYS, 0).reset_mode == engine.RESET_NONE
+        assert mk(f, engine.RESET_ALWAYS, 0, resumed=False).reset_mode == engine.RESET_NONE
+        p = mk(f, engine.RESET_IF_ZERO_CONSENSUS, 0, resumed=True)  # packed; the kernels fire it from epoch 1 only
+        assert (p.reset_mode, p.reset_epoch) == (engine.RESET_IF_ZERO_CONSENSUS, 0)
+        for e in (-1, 8):
+            assert mk(f, engine.RESET_ALWAYS, e, resumed=True).reset_mode == engine.RESET_NONE
+        assert mk(f, engine.RESET_ALWAYS, 3, resumed=True).reset_epoch == 3
+
+
 def test_reset_packing_equals_reference_statement():
     """the packed reset against the reference's own statements run
     in torch (simulation_utils.py:63-64 Yuma 3.1, :68-74 / :79-85 Yuma 3.2 / 4

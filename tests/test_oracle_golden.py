@@ -124,6 +124,45 @@ def test_oracle_run_medium(golden, sname):
         assert_close(div, g[f"{tag}__dividends"], what=f"{tag} dividends")
 
 
+SPLIT_E, SPLIT_E1, SPLIT_COL = 7, 3, 21
+
+
+@pytest.mark.parametrize("version,reset_epoch", [
+    ("Yuma 0 (subtensor)", None),
+    ("Yuma 1 (paper) - liquid alpha on", None),
+    ("Yuma 2 (Adrian-Fish)", None),
+    ("Yuma 3.1 (Rhef+reset)", SPLIT_E1),           # "always", at the first epoch of segment 2
+    ("Yuma 4 (Rhef+relative bonds)", SPLIT_E1 + 1),  # conditional, at epoch 1 of segment 2
+])
+def test_oracle_run_resumes_from_a_state(version, reset_epoch):
+    """run(E) == run(E1) followed by run(E - E1, B_init=B[E1-1], W_prev_init=
+    Wn[E1-1]), bitwise in Dn, C, I, B: the keywords seed exactly the state the
+    loop of run_simulation (simulation_utils.py:52-110) carries between epochs.
+    An "always" reset at the second segment's epoch 0 fires on the given state."""
+    E, E1, col = SPLIT_E, SPLIT_E1, SPLIT_COL
+    W = synth.weights(0x5917, E, 1, 16, 64)[:, 0]
+    S = synth.stakes(0x5917, E, 1, 16, period=3)[:, 0]
+    W[E1, :, col] = 0.0  # zero consensus at epoch E1: the conditional reset at E1 + 1 fires
+    liquid = version.endswith("liquid alpha on")
+    cfg = YumaConfig(yuma_params=YumaParams(liquid_alpha=liquid))
+    whole = orc.run(version, W, S, cfg, reset_epoch, col, return_weight=True)
+    a = orc.run(version, W[:E1], S[:E1], cfg, reset_epoch, col, return_weight=True)
+    rs = W[E1 - 1].sum(axis=1, dtype=np.float32)
+    Wn = (W[E1 - 1] / (rs + np.float32(1e-6))[:, None]).astype(np.float32)
+    np.testing.assert_array_equal(a["Wn"][E1 - 1], Wn)
+    r2 = None if reset_epoch is None else reset_epoch - E1
+    b = orc.run(version, W[E1:], S[E1:], cfg, r2, col, B_init=a["B"][E1 - 1], W_prev_init=Wn)
+    for k in ("Dn", "C", "I", "B"):
+        np.testing.assert_array_equal(a[k], whole[k][:E1], err_msg=f"{version} {k} segment 1")
+        np.testing.assert_array_equal(b[k], whole[k][E1:], err_msg=f"{version} {k} segment 2")
+    if reset_epoch is not None:  # the reset fired, in the whole run and so in segment 2
+        plain = orc.run(version, W, S, cfg)
+        assert whole["C"][E1, col] == 0.0
+        assert not np.array_equal(plain["B"][reset_epoch][:, col], whole["B"][reset_epoch][:, col])
+    # the state is not ignored: segment 2 from nothing is another run
+    assert not np.array_equal(orc.run(version, W[E1:], S[E1:], cfg)["B"], b["B"])
+
+
 @pytest.fixture(scope="module")
 def large_inputs(golden):
     g = golden("large.npz")

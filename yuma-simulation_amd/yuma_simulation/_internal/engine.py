@@ -235,8 +235,11 @@ def f32(x) -> float:
 
 def make_params(variant: int, config, *, maxint: int = 2**64 - 1, reset_mode: int = RESET_NONE,
                 reset_epoch: int | None = None, reset_index: int | None = None,
-                n_miners: int | None = None, n_epochs: int | None = None) -> YumaParamsC:
-    """Flatten a YumaConfig (yumas.py:29-45) into the engine's POD record."""
+                n_miners: int | None = None, n_epochs: int | None = None,
+                resumed: bool = False) -> YumaParamsC:
+    """Flatten a YumaConfig (yumas.py:29-45) into the engine's POD record.
+    resumed: the run starts from a caller's B_init, so a bond state exists at
+    epoch 0 and a reset at epoch 0 is reached (_pack_reset)."""
     p = YumaParamsC()
     p.variant = variant
     p.bisect_iters = bisect_iterations(config.consensus_precision)
@@ -282,7 +285,7 @@ def make_params(variant: int, config, *, maxint: int = 2**64 - 1, reset_mode: in
                 p.const_a, p.const_b = f32(a), f32(b)
                 p.liquid_mode = LIQUID_CONST_AB
         p.override_flags = flags
-    _pack_reset(p, reset_mode, reset_epoch, reset_index, n_miners, n_epochs)
+    _pack_reset(p, reset_mode, reset_epoch, reset_index, n_miners, n_epochs, resumed)
     return p
 
 
@@ -299,7 +302,7 @@ def config_key(config) -> tuple:
 
 def make_params_cached(variant: int, config, *, reset_mode: int = RESET_NONE, reset_epoch=None,
                        reset_index=None, n_miners: int | None = None, n_epochs: int | None = None,
-                       ckey: tuple | None = None) -> YumaParamsC:
+                       ckey: tuple | None = None, resumed: bool = False) -> YumaParamsC:
     """make_params memoised on every value it reads (the sheet builds 504
     records from 36 distinct configurations). Plain int / None reset fields
     only; anything else (a tensor-valued reset epoch) is built fresh. The
@@ -307,13 +310,13 @@ def make_params_cached(variant: int, config, *, reset_mode: int = RESET_NONE, re
     ckey: config_key(config), when the caller already has it."""
     if not all(x is None or type(x) is int for x in (reset_epoch, reset_index)):
         return make_params(variant, config, reset_mode=reset_mode, reset_epoch=reset_epoch,
-                           reset_index=reset_index, n_miners=n_miners, n_epochs=n_epochs)
-    key = (variant, reset_mode, reset_epoch, reset_index, n_miners, n_epochs,
+                           reset_index=reset_index, n_miners=n_miners, n_epochs=n_epochs, resumed=resumed)
+    key = (variant, reset_mode, reset_epoch, reset_index, n_miners, n_epochs, bool(resumed),
            config_key(config) if ckey is None else ckey)
     p = _PARAMS_CACHE.get(key)
     if p is None:
         p = make_params(variant, config, reset_mode=reset_mode, reset_epoch=reset_epoch,
-                        reset_index=reset_index, n_miners=n_miners, n_epochs=n_epochs)
+                        reset_index=reset_index, n_miners=n_miners, n_epochs=n_epochs, resumed=resumed)
         if len(_PARAMS_CACHE) > 65536:
             _PARAMS_CACHE.clear()
         _PARAMS_CACHE[key] = p
@@ -349,7 +352,8 @@ def _reset_epoch_value(reset_epoch) -> int | None:
     return None
 
 
-def _pack_reset(p: YumaParamsC, reset_mode: int, reset_epoch, reset_index, n_miners, n_epochs) -> None:
+def _pack_reset(p: YumaParamsC, reset_mode: int, reset_epoch, reset_index, n_miners, n_epochs,
+                resumed: bool = False) -> None:
     """The bond reset of run_simulation (simulation_utils.py:62-88) with the
     reference's Python indexing: `B_state[:, idx] = 0.0` and
     `server_consensus_weight[idx] == 0.0`, evaluated only at
@@ -368,7 +372,13 @@ def _pack_reset(p: YumaParamsC, reset_mode: int, reset_epoch, reset_index, n_min
     - index outside [-M, M): IndexError.
     The errors are raised only when the reference would reach the statement
     (reset_epoch in [1, n_epochs)). n_miners is needed for anything but a
-    plain in-range non-negative index."""
+    plain in-range non-negative index.
+
+    resumed: the run is given a B_init, so B_state exists at epoch 0 and the
+    statement is reached there too (reset_epoch in [0, n_epochs)). The
+    unconditional reset (Yuma 3.1) then zeroes the caller's state before epoch
+    0; the conditional ones read the previous epoch's consensus, which a run
+    does not have at epoch 0, and do not fire (the kernels test t >= 1)."""
     p.reset_mode = RESET_NONE
     p.reset_epoch = -1
     p.reset_index = 0
@@ -377,10 +387,10 @@ def _pack_reset(p: YumaParamsC, reset_mode: int, reset_epoch, reset_index, n_min
     try:
         epoch = _reset_epoch_value(reset_epoch)
     except _NoTruthValue as e:
-        if n_epochs is None or n_epochs >= 2:  # reached at epoch 1: the reference's own error
+        if n_epochs is None or n_epochs >= 2 or resumed:  # reached at epoch 1 (0): the reference's own error
             bool(1 == e.value)
         return
-    if epoch is None or epoch < 1 or (n_epochs is not None and epoch >= n_epochs):
+    if epoch is None or epoch < (0 if resumed else 1) or (n_epochs is not None and epoch >= n_epochs):
         return  # the statement never runs
     if not -2**31 <= epoch < 2**31:
         return  # beyond any int32 epoch count: never equal
@@ -499,6 +509,11 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     lib = load_library()
     if S.shape != (E, Nw, V):
         raise ValueError(f"S shape {tuple(S.shape)} does not match W {tuple(W.shape)}")
+    n_scen = len(params) if shared_inputs else Nw
+    for name, t in (("B_init", B_init), ("Wprev_init", Wprev_init)):
+        # the kernels index it n * V * M + row * M + m: a smaller tensor is read past its end
+        if t is not None and tuple(t.shape) != (n_scen, V, M):
+            raise ValueError(f"{name} shape {tuple(t.shape)} is not [N={n_scen}, V={V}, M={M}]")
     if shared_inputs:
         if Nw != 1:
             raise ValueError("shared_inputs takes W [E,1,V,M] and S [E,1,V]")

@@ -126,6 +126,16 @@ def _run_shards(variant: int, params: list, W_shards: list[torch.Tensor], S: tor
         raise ValueError(f"S shape {tuple(S.shape)} does not match W [E={E}, N={N}, V={V}]")
     if len(params) != N:
         raise ValueError("one parameter record per scenario is required")
+    for name, ts in (("B_init", B_init), ("Wprev_init", Wprev_init)):
+        if ts is None:
+            continue
+        if len(ts) != k:
+            raise ValueError(f"{name}: {len(ts)} tensors for {k} shards")
+        for i, t in enumerate(ts):
+            # before any stage is launched: the kernels would read a smaller tensor past its end
+            if tuple(t.shape) != (N, V, len(cols[i])):
+                raise ValueError(f"shard {i}: {name} shape {tuple(t.shape)} is not "
+                                 f"[N={N}, V={V}, {len(cols[i])} columns]")
     rust = variant == engine.VARIANT_RUST
     liquid = any(p.liquid_mode == engine.LIQUID_QUANTILE for p in params)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -224,6 +234,10 @@ def run_wide_local(variant: int, params: list, W: torch.Tensor, S: torch.Tensor,
     W_shards = [W[..., c.start:c.stop] for c in cols]
     B_init = kw.pop("B_init", None)
     Wprev = kw.pop("Wprev_init", None)
+    for name, t in (("B_init", B_init), ("Wprev_init", Wprev)):
+        # (the column slices below would hide extra columns from the per-shard check)
+        if t is not None and tuple(t.shape) != tuple(W.shape[1:]):
+            raise ValueError(f"{name} shape {tuple(t.shape)} is not [N, V, M] = {tuple(W.shape[1:])}")
     if B_init is not None:
         kw["B_init"] = [B_init[..., c.start:c.stop] for c in cols]
     if Wprev is not None:
