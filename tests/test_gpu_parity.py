@@ -429,6 +429,38 @@ def test_ragged_shapes_vs_oracle(V, M):
         assert_close(res.B_hist[:, 0].cpu().numpy(), ref["B"], rtol=1e-4, what=f"{variant} {V}x{M} B")
 
 
+@pytest.mark.parametrize("M", [68, 67])
+@pytest.mark.parametrize("V", [16, 40, 200, 300])
+@pytest.mark.parametrize("variant", ["yuma1", "yuma2"])
+def test_full_matrix_outputs_vs_oracle(variant, V, M):
+    """Wn / Wc / Tv / Wb / B_inst of a run against the oracle's epoch loop:
+    the materialising rank (k_rank_w; k_rank above 256 validators) and
+    k_bonds at each of the four row configurations (V = 200 and 300 leave a
+    ragged last row group). M = 68: vector form, two 64-miner tiles, the second
+    partial; M = 67: scalar form, which above 256 validators is also
+    k_consensus<1024, 16> without vector loads."""
+    E, N = 3, 2
+    W = synth.weights(0xF011 + V, E, N, V, M)
+    S = synth.stakes(0xF011 + V, E, N, V, period=2)
+    cfg = Y.YumaConfig()
+    vid = VARIANT_ID[variant]
+    res = engine.run(vid, [engine.make_params(vid, cfg)] * N, torch.from_numpy(W), torch.from_numpy(S),
+                     want_hist=True, want=("Wn", "Wc", "Tv", "Wb", "B_inst"))
+    torch.cuda.synchronize()
+    names = {"Wn": "weight", "Wc": "consensus_clipped_weight", "Tv": "validator_trust", "Wb": "weight_for_bond",
+             "B_inst": "validator_bond", "B_hist": "validator_ema_bond", "Dn": "validator_reward_normalized"}
+    got = {k: (res.extra[k] if k in res.extra else getattr(res, k)).cpu().numpy() for k in (*names, "C")}
+    for n in range(N):
+        B = W_prev = None
+        for t in range(E):
+            ref = orc.epoch(variant, W[t, n], S[t, n], B, cfg, W_prev=W_prev)
+            B, W_prev = ref["validator_ema_bond"], ref["weight"]
+            what = f"{variant} {V}x{M} scenario {n} epoch {t}"
+            np.testing.assert_array_equal(got["C"][t, n], ref["server_consensus_weight"], err_msg=what)
+            for k, rk in names.items():
+                assert_close(got[k][t, n], ref[rk], what=f"{what} {k}")
+
+
 @pytest.mark.parametrize("variant,version,V,M", [
     ("yuma1", "Yuma 1 (paper)", 128, 1024), ("yuma2", "Yuma 2 (Adrian-Fish)", 128, 1024),
     ("yuma3", "Yuma 3 (Rhef)", 128, 1024), ("yuma4", "Yuma 4 (Rhef+relative bonds)", 128, 1024),

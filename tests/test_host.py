@@ -420,6 +420,26 @@ def test_library_build_id_is_this_source():
     assert engine.build_id() == g.source_build_id()
 
 
+def test_every_ab_patch_set_applies_to_the_engine_source():
+    """tools/ab_build.py builds its A/B libraries from exact-match patches of
+    the engine source (tools/ab_patches.py): every set must still apply, each
+    `old` text found the stated number of times, so that a patch set cannot
+    rot unnoticed when the engine changes. String replacement only."""
+    import sys
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import ab_build
+
+    assert ab_build.PATCHES
+    src = open(ab_build.g.SRC).read()
+    for name in ab_build.PATCHES:
+        try:
+            out = ab_build.patched(name)
+        except SystemExit as e:  # patched() reports a count mismatch this way
+            pytest.fail(str(e))
+        assert out != src, name
+
+
 def test_bench_ignores_counter_records_of_another_build(tmp_path, monkeypatch):
     """a PMC / SQ record measured on another library build
     is never paired with this run's timings."""

@@ -1639,11 +1639,10 @@ __device__ __forceinline__ int iscan8_excl(int x, int r8) {
   return y - x;
 }
 
-// NP: wave pairs per block (2: a 64-miner tile per 4-wave block; 1: a
-// 32-miner group per 2-wave block, so a block barrier waits for the pair only)
-constexpr int kConsPairs = 2;
-template <bool VEC, int NP = 2, typename WT = float>
-__global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const WT* __restrict__ W,
+// Two wave pairs per block: a 64-miner tile per 4-wave block, not a 32-miner
+// group per 2-wave block (whose barrier would wait for one pair only).
+template <bool VEC, typename WT = float>
+__global__ __launch_bounds__(256, 3) void k_consensus_p(const WT* __restrict__ W,
                                                      const float* __restrict__ rsd,
                                                      const float* __restrict__ sn,
                                                      const int* __restrict__ sx,
@@ -1654,7 +1653,7 @@ __global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const WT* __restric
                                                      const int* __restrict__ crep,
                                                      const float4* __restrict__ rq4) {
   constexpr int R = 16, HR = 8 * R;  // rows per lane, rows per half
-  constexpr int NWV = 2 * NP;         // waves per block
+  constexpr int NP = 2, NWV = 2 * NP;  // wave pairs, waves per block
   __shared__ __attribute__((aligned(16))) unsigned hb[NP * 32 * kHS];  // per pair: 32 columns
   __shared__ __attribute__((aligned(16))) float rl[NWV][3 * HR];        // per wave: sums, stakes, 1 / sums
   __shared__ float xf[2][NWV][32];  // float exchange, double-buffered
@@ -1663,9 +1662,8 @@ __global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const WT* __restric
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int pair = wave >> 1, h = wave & 1, pw = wave ^ 1;
   const int cq = lane >> 3, rg = lane & 7;
-  const int ctiles = NP == 2 ? tiles : (M + 31) / 32;  // column groups of 32 NP miners per slice
-  const long long slice = slice0 + blockIdx.x / ctiles;
-  const int tile = blockIdx.x % ctiles;
+  const long long slice = slice0 + blockIdx.x / tiles;
+  const int tile = blockIdx.x % tiles;
   const int n = (int)(slice % N);
   if (dup_slice(crep, slice, N)) return;  // block-uniform
   const int m = tile * (32 * NP) + pair * 32 + cq * 4;
@@ -1912,7 +1910,7 @@ __global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const WT* __restric
     // search needs no activity flags and no closing all-idle pass
     int wmax;
     {
-      const int pl = NP == 2 ? lane >> 5 : 0, cl = lane & 31;
+      const int pl = lane >> 5, cl = lane & 31;
       int lo, hi;
       bracket_of(max(xi[0][2 * pl][cl], xi[0][2 * pl + 1][cl]), min(xi[1][2 * pl][cl], xi[1][2 * pl + 1][cl]),
                  xf[0][2 * pl][0] + xf[0][2 * pl + 1][0], lo, hi);
@@ -2024,7 +2022,7 @@ __global__ __launch_bounds__(128 * NP, 3) void k_consensus_p(const WT* __restric
 
 // Clip + rank (yumas.py:214-217; Yuma2 clips W_prev :328), wave-owned columns.
 // rpart[slice][tile] = sum over the tile's 64 miners (wave sums, waves in order).
-template <int R, bool VEC, bool YUMA2, bool FULL>
+template <int R, bool VEC, bool YUMA2>
 __global__ __launch_bounds__(256) void k_rank_w(
     const float* __restrict__ W, const float* __restrict__ rsd, const float* __restrict__ sn,
     const float* __restrict__ C, const float* __restrict__ Wprev_init, int yuma2_unused, int N, int V,
@@ -2079,7 +2077,7 @@ __global__ __launch_bounds__(256) void k_rank_w(
       wc[c] = vmin(src[c], Cc[c]);
       acc[c] = acc[c] + s[i] * wc[c];
     }
-    if (FULL && row < V) {
+    if (row < V) {
       if (Wn_out != nullptr) store4<VEC>(Wn_out + slice * VM + (long long)row * M, m, M, wn[i]);
       if (Wc_out != nullptr) store4<VEC>(Wc_out + slice * VM + (long long)row * M, m, M, wc);
     }
@@ -2096,7 +2094,7 @@ __global__ __launch_bounds__(256) void k_rank_w(
   for (int c = 0; c < 4; ++c) ws = ws + acc[c];
   ws = qsum4(ws);
   if (L.lane == 0) wsums[L.wave] = ws;
-  if (FULL && tvc != nullptr) {
+  if (tvc != nullptr) {
     // full-output mode only: validator-trust partials over this tile's 64
     // miners (quads xor 1, 2; then waves in order via LDS); V <= 256 here
     __shared__ float tvs[2][4][256];
@@ -2446,7 +2444,6 @@ __global__ __launch_bounds__(256, 1) void k_rank_s(const WT* __restrict__ W,
 // profiles/r05/ab_rank_wide.txt), so k_rank_s stays there.
 // BIGV (above kRegRows validators): the row sums, reciprocals and stakes are
 // read per row from memory instead of the LDS staging.
-constexpr int kRankWide = 1;  // launch the wide form (0: k_rank_s everywhere)
 template <bool VEC, bool YUMA2 = false, bool BCS = false, bool BIGV = false, typename WT = float>
 __global__ __launch_bounds__(256, 1) void k_rank_sw(const WT* __restrict__ W,
                                                  const float* __restrict__ rsd,
@@ -3205,9 +3202,10 @@ __global__ __launch_bounds__(256) void k_incentive(float* __restrict__ Rio,
 // Phase 2: bond recurrence over the epochs [t0, t1) of a chunk, one block per
 // (scenario, row block, 64-miner tile); the bond tile stays in registers.
 //   VARIANT 3 (yumas.py:452-472) and 4 (:570-586) are element-wise, so a block
-//   owns R*G rows of the tile. VARIANT 0/1/2 normalise bond columns over all
-//   validators (yumas.py:113-116,147-149; :228; :342), so a block owns the
-//   whole column (single row block).
+//   owns some rows of the tile (k_bonds_elem, k_bonds_grp). VARIANT 0/1/2
+//   normalise bond columns over all validators (yumas.py:113-116,147-149;
+//   :228; :342), so a block owns the whole column (k_bonds, k_bonds_cn: a
+//   single row block).
 // dpart[slice][tile][v] = sum over the tile's columns of B_state * I.
 // ---------------------------------------------------------------------------
 struct BondArgs {
@@ -3278,11 +3276,15 @@ __device__ __forceinline__ bool reset_c_zero(const BondArgs& A, int n, int mode,
 
 template <int VARIANT, int NT, int R, bool VEC>
 __global__ __launch_bounds__(NT) void k_bonds(BondArgs A) {
+  static_assert(VARIANT == YUMA_VARIANT_RUST || VARIANT == YUMA_VARIANT_YUMA1 || VARIANT == YUMA_VARIANT_YUMA2,
+                "k_bonds serves the column-normalised variants");
   constexpr int NW = NT / 64, G = NT / 16;
-  constexpr bool COLNORM = (VARIANT == YUMA_VARIANT_RUST || VARIANT == YUMA_VARIANT_YUMA1 ||
-                            VARIANT == YUMA_VARIANT_YUMA2);
   __shared__ float4 red[2][NW * 16];
   const Lay L = lay();
+  // (A.rowblocks is 1 here, a block owns whole columns. The index stays: without
+  // it the compiler allocates the 16-row forms differently -- Yuma 0, 65-256
+  // validators, scalar form 132 -> 479 VGPR spills, 3.3 -> 4.4 ms per 100 epochs
+  // at 256 x 4094, profiles/r06/ab/ab_dispatch_refactor.txt)
   const int tile = blockIdx.x % A.tiles;
   const int rb = (blockIdx.x / A.tiles) % A.rowblocks;
   const int n = blockIdx.x / (A.tiles * A.rowblocks);
@@ -3356,27 +3358,9 @@ __global__ __launch_bounds__(NT) void k_bonds(BondArgs A) {
 
   for (int t = A.t0; t < A.t1; ++t) {
     const long long slice = (long long)t * N + n;
-    // bond resets of run_simulation (simulation_utils.py:62-88), applied to
-    // the state before this epoch's update
-    const bool reset_all = (p.flags & YUMA_FLAG_RESET_ALL_COLUMNS) != 0;
-    if ((VARIANT == YUMA_VARIANT_YUMA3 || VARIANT == YUMA_VARIANT_YUMA4) && has_old &&
-        p.reset_mode != YUMA_RESET_NONE && t == p.reset_epoch &&
-        (reset_all || (p.reset_index >= 0 && p.reset_index < M))) {
-      bool fire = p.reset_mode == YUMA_RESET_ALWAYS;
-      if (p.reset_mode == YUMA_RESET_IF_ZERO_CONSENSUS && t >= 1 && !reset_all)
-        fire = A.C[(slice - N) * M + p.reset_index] == 0.0f;
-      const int c = p.reset_index - m;
-      if (fire && (reset_all || (c >= 0 && c < 4)))
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-#pragma unroll
-          for (int cc = 0; cc < 4; ++cc)
-            if (reset_all || cc == c) B[i][cc] = 0.0f;
-        }
-    }
     float Ic[4], Cc[4], bac[4], omba[4];
     load4_vec(A.I + slice * M, m, M, Ic);
-    if (COLNORM) load4_vec(A.C + slice * M, m, M, Cc);
+    load4_vec(A.C + slice * M, m, M, Cc);
     if (p.liquid_mode != YUMA_LIQUID_OFF) {
       load4_vec(A.ba + slice * M, m, M, bac);
 #pragma unroll
@@ -3422,99 +3406,71 @@ __global__ __launch_bounds__(NT) void k_bonds(BondArgs A) {
       if (row0 + G * i >= V) s[i] = 0.0f;
     }
 
-    if (VARIANT == YUMA_VARIANT_YUMA3) {
+    float num[R][4];
+    float colsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-      for (int i = 0; i < R; ++i) {
-        const float cap = s[i] * p.maxint;
-        const float ca = p.capacity_alpha * cap;
+    for (int i = 0; i < R; ++i) {
+      const int row = row0 + G * i;
+      float src[4], wc[4], wb[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        src[c] = (VARIANT == YUMA_VARIANT_YUMA2 && have_wp) ? Wp[i][c] : wn[i][c];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) wc[c] = tmin(src[c], Cc[c]);
+      if (VARIANT == YUMA_VARIANT_RUST) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) num[i][c] = s[i] * wc[c];
+      } else {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          const float rem = tmax(cap - B[i][c], 0.0f);
-          const float pc = tmin(ca, rem);
-          const float purchase = pc * wn[i][c];
-          const float nb = p.decay_keep * B[i][c] + purchase;
-          B[i][c] = tmin(nb, cap);
+          wb[c] = p.one_minus_bond_penalty * src[c] + p.bond_penalty * wc[c];
+          num[i][c] = s[i] * wb[c];
         }
+        if (A.Wb_out != nullptr && row < V)
+          store4<VEC>(A.Wb_out + slice * VM + (long long)row * M, m, M, wb);
       }
-    } else if (VARIANT == YUMA_VARIANT_YUMA4) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) colsum[c] = colsum[c] + num[i][c];
+    }
+    col_reduce4<NW>(colsum, red[0], L);
+    float den[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      den[c] = (VARIANT == YUMA_VARIANT_RUST) ? colsum[c] + 1e-6f : colsum[c];
+    float ema_sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+      const int row = row0 + G * i;
+      float binst[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float b = num[i][c] / den[c];
+        binst[c] = (VARIANT == YUMA_VARIANT_RUST) ? nan_to_num(b, 0.0f) : nan_to_num(b, 0.0f);
+      }
+      if (A.Binst_out != nullptr && row < V)
+        store4<VEC>(A.Binst_out + slice * VM + (long long)row * M, m, M, binst);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        float e = binst[c];
+        if (has_old) e = bac[c] * binst[c] + omba[c] * B[i][c];
+        if (row >= V) e = 0.0f;
+        B[i][c] = e;
+        ema_sum[c] = ema_sum[c] + e;
+      }
+    }
+    if (VARIANT == YUMA_VARIANT_RUST) {
+      col_reduce4<NW>(ema_sum, red[1], L);
 #pragma unroll
       for (int i = 0; i < R; ++i)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float bd = B[i][c] * omba[c];
-          const float rem = tmax(1.0f - bd, 0.0f);
-          const float pi = bac[c] * wn[i][c];
-          const float nb = bd + tmin(pi, rem);
-          B[i][c] = tmin(nb, 1.0f);
-        }
-    } else {
-      // column-normalised variants
-      float num[R][4];
-      float colsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int c = 0; c < 4; ++c) B[i][c] = nan_to_num(B[i][c] / (ema_sum[c] + 1e-6f), 0.0f);
+    }
+    if (VARIANT == YUMA_VARIANT_YUMA2) {
 #pragma unroll
-      for (int i = 0; i < R; ++i) {
-        const int row = row0 + G * i;
-        float src[4], wc[4], wb[4];
+      for (int i = 0; i < R; ++i)
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-          src[c] = (VARIANT == YUMA_VARIANT_YUMA2 && have_wp) ? Wp[i][c] : wn[i][c];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) wc[c] = tmin(src[c], Cc[c]);
-        if (VARIANT == YUMA_VARIANT_RUST) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) num[i][c] = s[i] * wc[c];
-        } else {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            wb[c] = p.one_minus_bond_penalty * src[c] + p.bond_penalty * wc[c];
-            num[i][c] = s[i] * wb[c];
-          }
-          if (A.Wb_out != nullptr && row < V)
-            store4<VEC>(A.Wb_out + slice * VM + (long long)row * M, m, M, wb);
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) colsum[c] = colsum[c] + num[i][c];
-      }
-      col_reduce4<NW>(colsum, red[0], L);
-      float den[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        den[c] = (VARIANT == YUMA_VARIANT_RUST) ? colsum[c] + 1e-6f : colsum[c];
-      float ema_sum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int i = 0; i < R; ++i) {
-        const int row = row0 + G * i;
-        float binst[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float b = num[i][c] / den[c];
-          binst[c] = (VARIANT == YUMA_VARIANT_RUST) ? nan_to_num(b, 0.0f) : nan_to_num(b, 0.0f);
-        }
-        if (A.Binst_out != nullptr && row < V)
-          store4<VEC>(A.Binst_out + slice * VM + (long long)row * M, m, M, binst);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float e = binst[c];
-          if (has_old) e = bac[c] * binst[c] + omba[c] * B[i][c];
-          if (row >= V) e = 0.0f;
-          B[i][c] = e;
-          ema_sum[c] = ema_sum[c] + e;
-        }
-      }
-      if (VARIANT == YUMA_VARIANT_RUST) {
-        col_reduce4<NW>(ema_sum, red[1], L);
-#pragma unroll
-        for (int i = 0; i < R; ++i)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) B[i][c] = nan_to_num(B[i][c] / (ema_sum[c] + 1e-6f), 0.0f);
-      }
-      if (VARIANT == YUMA_VARIANT_YUMA2) {
-#pragma unroll
-        for (int i = 0; i < R; ++i)
-#pragma unroll
-          for (int c = 0; c < 4; ++c) Wp[i][c] = wn[i][c];
-        have_wp = true;
-      }
+        for (int c = 0; c < 4; ++c) Wp[i][c] = wn[i][c];
+      have_wp = true;
     }
     has_old = true;
 
@@ -3531,7 +3487,7 @@ __global__ __launch_bounds__(NT) void k_bonds(BondArgs A) {
       d = sum_row16(d);
       if (L.c4 == 0 && row < V) A.dpart[(slice * A.tiles + tile) * V + row] = d;
     }
-    if (COLNORM) __syncthreads();  // red[] reuse across epochs
+    __syncthreads();  // red[] reuse across epochs
   }
 #pragma unroll
   for (int i = 0; i < R; ++i) {
@@ -4422,8 +4378,7 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
 // (profiles/r04/ab_round3.txt, ab_round4.txt).
 // ---------------------------------------------------------------------------
 constexpr int kGrpWaves = 3;  // minimum waves per SIMD of the sweep scan
-constexpr bool kGrpPark = true;  // dividend partials parked per wave in LDS
-constexpr int kGrpDB = 32;       // ... epochs per flush
+constexpr int kGrpDB = 32;  // epochs of dividend partials parked per wave in LDS per flush
 // LQ: 0 = every scenario of the block has a fixed bond_alpha (block-uniform
 // operands), 2 = every one is liquid (per-miner bond_alpha), 1 = mixed.
 // BND (Yuma 4): the wave's bond state starts in [0, 1] (or NaN), every
@@ -4549,7 +4504,8 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
   float ri[K][4], rba[K][4];
   const float* fI[K];
   const float* fB[K];
-  float* pD[K];  // this epoch's dividend partials
+  float* pD[K];  // this epoch's dividend partials (not read: they are parked, below; the
+                 // compiler's schedule of the scan changes without this walk)
   float* pH[K];  // this epoch's bond history, if stored
   constexpr bool hist = HIST;
 #pragma unroll
@@ -4602,7 +4558,7 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
   // rows x the wave's 4 row groups) and written out as 16-byte row runs when
   // the buffer fills or the launch ends: no global store in the epoch loop
   // and no block barrier (a block-wide version lost in round 4)
-  float* dpb = dpark + (kGrpPark ? L.wave * (kGrpDB * K * R * 4) : 0);
+  float* dpb = dpark + L.wave * (kGrpDB * K * R * 4);
   int tq = A.t0;  // first epoch held in the wave's buffer
   auto flush_d = [&](int t) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -4728,11 +4684,7 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
           for (int c = 0; c < 4; ++c) d = d + B[k][i][c] * ic[c];
           d = m < M ? d : 0.0f;
           d = wsum16(d);
-          if constexpr (kGrpPark) {
-            if (L.c4 == 0) dpb[(((t - tq) * K + k) * R + i) * 4 + (L.lane >> 4)] = d;
-          } else {
-            if (L.c4 == 0 && row < V) pD[k][G * i] = d;
-          }
+          if (L.c4 == 0) dpb[(((t - tq) * K + k) * R + i) * 4 + (L.lane >> 4)] = d;
         }
         fetch_s(k, t + 2 < A.t1);
         pD[k] += sD;
@@ -4743,9 +4695,7 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
       // incentive does not wait for the rows two epochs ahead (c3 bonds
       // 6.69-6.73 -> 6.61-6.62 ms, profiles/r05/ab_grp.txt)
       fetch(kk, t + P + 1 < A.t1);
-      if constexpr (kGrpPark) {
-        if (t - tq == kGrpDB - 1 || t == A.t1 - 1) flush_d(t);  // wave-uniform
-      }
+      if (t - tq == kGrpDB - 1 || t == A.t1 - 1) flush_d(t);  // wave-uniform
       has_old = true;
     }
   }
@@ -4762,7 +4712,7 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
 
 template <int VARIANT, int K, int R, int P, bool HIST>
 __global__ __launch_bounds__(256, kGrpWaves) void k_bonds_grp(BondArgs A) {
-  __shared__ float dpark[kGrpPark ? 4 * kGrpDB * K * R * 4 : 1];
+  __shared__ float dpark[4 * kGrpDB * K * R * 4];
   const int n0 = (blockIdx.x / (A.tiles * A.rowblocks)) * K;
   unsigned liquid_mask = 0;
 #pragma unroll
@@ -5273,6 +5223,13 @@ RowCfg row_cfg(int V) {
 #define YK_LAUNCH(kernel, grid, block, stream, ...) \
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (hipStream_t)(stream), __VA_ARGS__)
 
+// A run-time flag as a template argument: f(std::true_type{}) or
+// f(std::false_type{}), so that a launch is written once for both values.
+template <typename F>
+auto with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
+
 template <int R, bool VEC, typename WT>
 void launch_consensus_w(long long nblocks, hipStream_t st, const WT* W, const float* rsd,
                         const float* sn, const int* sx, const yuma_params_t* prm, int N, int V,
@@ -5286,19 +5243,16 @@ template <bool VEC>
 void launch_consensus_mc(RowCfg rc, long long nblocks, hipStream_t st, const float* W, const float* rsd,
                          const float* sn, const int* sx, const yuma_params_t* prm, int N, int V, int M,
                          long long t0, int tiles, double* craw, const int* clist, int G) {
+  auto go = [&](auto kern) {
+    YK_LAUNCH(kern, nblocks, 256, st, W, rsd, sn, sx, prm, N, V, M, t0, tiles, craw, clist, G);
+  };
   switch (rc) {
     case RC_256_1:
-      YK_LAUNCH((yk::k_consensus_mc<1, VEC>), nblocks, 256, st, W, rsd, sn, sx, prm, N, V, M, t0, tiles, craw,
-                clist, G);
-      return;
+      return go(yk::k_consensus_mc<1, VEC>);
     case RC_256_4:
-      YK_LAUNCH((yk::k_consensus_mc<4, VEC>), nblocks, 256, st, W, rsd, sn, sx, prm, N, V, M, t0, tiles, craw,
-                clist, G);
-      return;
+      return go(yk::k_consensus_mc<4, VEC>);
     default:
-      YK_LAUNCH((yk::k_consensus_mc<16, VEC>), nblocks, 256, st, W, rsd, sn, sx, prm, N, V, M, t0, tiles, craw,
-                clist, G);
-      return;
+      return go(yk::k_consensus_mc<16, VEC>);
   }
 }
 
@@ -5310,9 +5264,8 @@ void launch_consensus(RowCfg rc, long long nblocks, hipStream_t st, const WT* W,
                       const yuma_params_t* prm, int N, int V, int M, long long slice0, int tiles,
                       double* craw, float* P, int wsh, const int* crep,
                       const float4* rq4 = nullptr) {
-  constexpr bool F32 = std::is_same_v<WT, float>;
   if (V > yk::kRegRows) {  // the column streamed per search pass
-    if constexpr (F32)
+    if constexpr (std::is_same_v<WT, float>)
       YK_LAUNCH(yk::k_consensus_big<VEC>, nblocks, 256, st, W, rsd, sn, prm, N, V, M, slice0, tiles, craw, P,
                 wsh, crep);
     return;
@@ -5336,44 +5289,31 @@ void launch_consensus(RowCfg rc, long long nblocks, hipStream_t st, const WT* W,
       // kernel for exact-stake inputs (the histogram / bisection sums are
       // exact); for generic float stakes the two kernels' F sums may differ
       // in the last bit at a tie, inside the tie window the tests allow.
-      if (VEC && !wsh && P == nullptr) {
-        constexpr int NP = yk::kConsPairs;
-        const long long nb = NP == 2 ? nblocks : nblocks / tiles * ((M + 31) / 32);
-        YK_LAUNCH((yk::k_consensus_p<true, NP, WT>), nb, 128 * NP, st, W, rsd, sn, sx, prm, N, V, M, slice0, tiles,
+      if (VEC && !wsh && P == nullptr)
+        YK_LAUNCH((yk::k_consensus_p<true, WT>), nblocks, 256, st, W, rsd, sn, sx, prm, N, V, M, slice0, tiles,
                   craw, P, wsh, crep, rq4);
-      }
       else
         launch_consensus_w<16, VEC>(nblocks, st, W, rsd, sn, sx, prm, N, V, M, slice0, tiles, craw, P, wsh,
                                     crep);
       return;
-    default:
-      break;
-  }
-  switch (rc) {
-    case RC_256_1:
-      if constexpr (F32)
-        YK_LAUNCH((yk::k_consensus<256, 1, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
-                  slice0, tiles, craw, P, wsh, crep);
-      break;
-    case RC_256_4:
-      if constexpr (F32)
-        YK_LAUNCH((yk::k_consensus<256, 4, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
-                  slice0, tiles, craw, P, wsh, crep);
-      break;
-    case RC_256_16:
-      if constexpr (F32)
-        YK_LAUNCH((yk::k_consensus<256, 16, VEC>), nblocks, 256, st, W, rsd, sn, prm, N, V, M,
-                  slice0, tiles, craw, P, wsh, crep);
-      break;
-    case RC_1024_16:
+    case RC_1024_16:  // 257-1024 validators: the column across the block's 16 waves
       YK_LAUNCH((yk::k_consensus<1024, 16, VEC, WT>), nblocks, 1024, st, W, rsd, sn, prm, N, V, M,
                 slice0, tiles, craw, P, wsh, crep);
-      break;
+      return;
   }
 }
 
-// csb (streaming rank only, Yuma / Yuma2): also form the bond column sums
-// Σ_v S·W_b per slice and miner (k_rank_s BCS) for the element-wise bond scan
+// The rank pass. Up to kRegRows validators, by what is asked of it:
+//   full (Wn / Wc / T_v materialised): k_rank_w (<= 256 validators), k_rank;
+//   bond column sums (csb) or >= 16384 miners: k_rank_sw on 256-miner blocks --
+//     the wide form (c4 rank 1.15 -> 1.10 ms; c2's plain rank is a tie, 0.70
+//     both, profiles/r05/ab_rank_wide.txt, ab_c4_rank.txt);
+//   a shared-input sweep's class list (clist): k_rank_mc, every class per block;
+//   else k_rank_s on 64-miner tiles.
+// Above kRegRows (streamed rows): k_rank_sw with per-row loads, then k_full_big
+// for the full outputs.
+// csb (Yuma / Yuma2): also form the bond column sums Σ_v S·W_b per slice and
+// miner, and csr, for the element-wise bond scan.
 template <bool VEC>
 void launch_rank(RowCfg rc, long long nblocks, hipStream_t st, const float* W, const float* rsd,
                  const float* sn, const float* C, const float* Wprev_init, int yuma2, int N,
@@ -5382,111 +5322,62 @@ void launch_rank(RowCfg rc, long long nblocks, hipStream_t st, const float* W, c
                  float* csb = nullptr, float* csr = nullptr, const yuma_params_t* prm = nullptr,
                  const int* clist = nullptr) {
   const bool full = Wn != nullptr || Wc != nullptr || tvc != nullptr;
-  if (V > yk::kRegRows) {  // streamed rows: the wide rank with per-row loads, plus the full outputs
-    const long long nb = nblocks / tiles * ((M + 255) / 256);
-    if (yuma2 && csb)
-      YK_LAUNCH((yk::k_rank_sw<VEC, true, true, true>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, nullptr, Wprev_init, csb, csr, prm);
-    else if (yuma2)
-      YK_LAUNCH((yk::k_rank_sw<VEC, true, false, true>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, nullptr, Wprev_init, nullptr, nullptr, prm);
-    else if (csb)
-      YK_LAUNCH((yk::k_rank_sw<VEC, false, true, true>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, full ? nullptr : crep, nullptr, csb, csr, prm);
-    else
-      YK_LAUNCH((yk::k_rank_sw<VEC, false, false, true>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, full ? nullptr : crep, nullptr, nullptr, nullptr, prm);
-    if (full) {
-      if (yuma2)
-        YK_LAUNCH((yk::k_full_big<VEC, true>), nblocks, 256, st, W, rsd, C, N, V, M, slice0, tiles, wsh,
-                  Wprev_init, Wn, Wc, tvc, tvn);
-      else
-        YK_LAUNCH((yk::k_full_big<VEC, false>), nblocks, 256, st, W, rsd, C, N, V, M, slice0, tiles, wsh,
-                  Wprev_init, Wn, Wc, tvc, tvn);
-    }
+  const bool bcs = csb != nullptr;
+  // k_rank_s / k_rank_sw<VEC, YUMA2, BCS, ..>: kernel(Y2, BCS) names the
+  // instantiation. The rank of a class representative serves its duplicates
+  // (crep) except under Yuma2 (W_prev is per scenario) and the full outputs.
+  auto stream = [&](long long nb, auto kernel) {
+    with_bool(yuma2 != 0, [&](auto Y2) {
+      with_bool(bcs, [&](auto BCS) {
+        auto kern = kernel(Y2, BCS);
+        YK_LAUNCH(kern, nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles, R, rpart, wsh,
+                  (yuma2 || full) ? nullptr : crep, yuma2 ? Wprev_init : nullptr, csb, bcs ? csr : nullptr, prm);
+      });
+    });
+  };
+  const long long nb256 = nblocks / tiles * ((M + 255) / 256);  // 256-miner column blocks
+  if (V > yk::kRegRows) {
+    stream(nb256, [](auto Y2, auto BCS) {
+      return yk::k_rank_sw<VEC, decltype(Y2)::value, decltype(BCS)::value, true>;
+    });
+    if (full)
+      with_bool(yuma2 != 0, [&](auto Y2) {
+        YK_LAUNCH((yk::k_full_big<VEC, decltype(Y2)::value>), nblocks, 256, st, W, rsd, C, N, V, M, slice0, tiles,
+                  wsh, Wprev_init, Wn, Wc, tvc, tvn);
+      });
     return;
   }
-  // the wide form for the ranks that also form bond column sums, and for wide
-  // subnets (c4 rank 1.15 -> 1.10 ms; c2's plain rank is a tie, 0.70 both,
-  // profiles/r05/ab_rank_wide.txt, ab_c4_rank.txt)
-  if (!full && (csb || M >= 16384) && yk::kRankWide) {  // streaming rank on 256-miner column blocks
-    const long long nb = nblocks / tiles * ((M + 255) / 256);
-    if (yuma2 && csb)
-      YK_LAUNCH((yk::k_rank_sw<VEC, true, true>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, nullptr, Wprev_init, csb, csr, prm);
-    else if (yuma2)
-      YK_LAUNCH((yk::k_rank_sw<VEC, true>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles, R,
-                rpart, wsh, nullptr, Wprev_init, nullptr, nullptr, prm);
-    else if (csb)
-      YK_LAUNCH((yk::k_rank_sw<VEC, false, true>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, crep, nullptr, csb, csr, prm);
-    else
-      YK_LAUNCH((yk::k_rank_sw<VEC, false>), nb, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles, R,
-                rpart, wsh, crep, nullptr, nullptr, nullptr, prm);
+  if (!full) {
+    if (bcs || M >= 16384)
+      stream(nb256, [](auto Y2, auto BCS) {
+        return yk::k_rank_sw<VEC, decltype(Y2)::value, decltype(BCS)::value>;
+      });
+    else if (clist != nullptr && !yuma2) {
+      const int G = N < yk::kMcGroups ? N : yk::kMcGroups;
+      YK_LAUNCH((yk::k_rank_mc<VEC, 4>), nblocks / N * G, 256, st, W, rsd, sn, C, N, V, M, slice0 / N, tiles, R,
+                rpart, clist, G);
+    } else
+      stream(nblocks, [](auto Y2, auto BCS) {
+        return yk::k_rank_s<VEC, decltype(Y2)::value, decltype(BCS)::value>;
+      });
     return;
   }
-  if (!full && clist != nullptr && !yuma2 && !csb) {  // shared-input sweep: every class per block
-    const int G = N < yk::kMcGroups ? N : yk::kMcGroups;
-    YK_LAUNCH((yk::k_rank_mc<VEC, 4>), nblocks / N * G, 256, st, W, rsd, sn, C, N, V, M, slice0 / N, tiles, R,
-              rpart, clist, G);
-    return;
-  }
-  if (!full) {  // streaming rank; k_rank_w also materialises Wn / Wc / T_v
-    if (yuma2 && csb)  // per scenario: W_prev (the caller's) is not shared by a consensus class
-      YK_LAUNCH((yk::k_rank_s<VEC, true, true>), nblocks, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, nullptr, Wprev_init, csb, csr, prm);
-    else if (yuma2)
-      YK_LAUNCH((yk::k_rank_s<VEC, true>), nblocks, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles, R,
-                rpart, wsh, nullptr, Wprev_init, nullptr, nullptr, prm);
-    else if (csb)
-      YK_LAUNCH((yk::k_rank_s<VEC, false, true>), nblocks, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles,
-                R, rpart, wsh, crep, nullptr, csb, csr, prm);
-    else
-      YK_LAUNCH((yk::k_rank_s<VEC, false>), nblocks, 256, st, W, rsd, sn, C, N, V, M, slice0, tiles, R,
-                rpart, wsh, crep, nullptr, nullptr, nullptr, prm);
-    return;
-  }
-  auto go = [&](auto kern) {
-    YK_LAUNCH(kern, nblocks, 256, st, W, rsd, sn, C, Wprev_init, yuma2, N, V, M, slice0, tiles, R,
+  auto go = [&](auto kern, int nt) {
+    YK_LAUNCH(kern, nblocks, nt, st, W, rsd, sn, C, Wprev_init, yuma2, N, V, M, slice0, tiles, R,
               rpart, Wn, Wc, tvc, tvn, wsh);
   };
-#define YK_RANKW(RR)                                                   \
-  if (yuma2) {                                                         \
-    if (full) go(yk::k_rank_w<RR, VEC, true, true>);                   \
-    else go(yk::k_rank_w<RR, VEC, true, false>);                       \
-  } else {                                                             \
-    if (full) go(yk::k_rank_w<RR, VEC, false, true>);                  \
-    else go(yk::k_rank_w<RR, VEC, false, false>);                      \
-  }                                                                    \
-  return;
-  switch (rc) {  // wave-owned columns up to 256 validators
-    case RC_256_1:
-      YK_RANKW(1)
-    case RC_256_4:
-      YK_RANKW(4)
-    case RC_256_16:
-      YK_RANKW(16)
-    default:
-      break;
-  }
-  switch (rc) {
-    case RC_256_1:
-      YK_LAUNCH((yk::k_rank<256, 1, VEC>), nblocks, 256, st, W, rsd, sn, C, Wprev_init, yuma2,
-                N, V, M, slice0, tiles, R, rpart, Wn, Wc, tvc, tvn, wsh);
-      break;
-    case RC_256_4:
-      YK_LAUNCH((yk::k_rank<256, 4, VEC>), nblocks, 256, st, W, rsd, sn, C, Wprev_init, yuma2,
-                N, V, M, slice0, tiles, R, rpart, Wn, Wc, tvc, tvn, wsh);
-      break;
-    case RC_256_16:
-      YK_LAUNCH((yk::k_rank<256, 16, VEC>), nblocks, 256, st, W, rsd, sn, C, Wprev_init, yuma2,
-                N, V, M, slice0, tiles, R, rpart, Wn, Wc, tvc, tvn, wsh);
-      break;
-    case RC_1024_16:
-      YK_LAUNCH((yk::k_rank<1024, 16, VEC>), nblocks, 1024, st, W, rsd, sn, C, Wprev_init,
-                yuma2, N, V, M, slice0, tiles, R, rpart, Wn, Wc, tvc, tvn, wsh);
-      break;
-  }
+  if (rc == RC_1024_16) return go(yk::k_rank<1024, 16, VEC>, 1024);
+  with_bool(yuma2 != 0, [&](auto Y2) {  // wave-owned columns up to 256 validators
+    constexpr bool kY2 = decltype(Y2)::value;
+    switch (rc) {
+      case RC_256_1:
+        return go(yk::k_rank_w<1, VEC, kY2>, 256);
+      case RC_256_4:
+        return go(yk::k_rank_w<4, VEC, kY2>, 256);
+      default:
+        return go(yk::k_rank_w<16, VEC, kY2>, 256);
+    }
+  });
 }
 
 // uint16 weights (yuma_u16_native: Yuma 3 / Yuma 4, <= kRegRows validators, no
@@ -5497,7 +5388,7 @@ template <bool VEC>
 void launch_rank(RowCfg, long long nblocks, hipStream_t st, const uint16_t* W, const float* rsd,
                  const float* sn, const float* C, int N, int V, int M, long long slice0, int tiles,
                  float* R, float* rpart) {
-  if (M >= 16384 && yk::kRankWide) {
+  if (M >= 16384) {
     const long long nb = nblocks / tiles * ((M + 255) / 256);
     YK_LAUNCH((yk::k_rank_sw<VEC, false, false, false, uint16_t>), nb, 256, st, W, rsd, sn, C, N, V, M,
               slice0, tiles, R, rpart, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -5513,22 +5404,22 @@ void launch_rank(RowCfg, long long nblocks, hipStream_t st, const uint16_t* W, c
 // small subnets and the full-output epoch (W_b / instantaneous bonds stored)
 // k_bonds on 64-miner tiles. Returns the dividend-partial layout and sets
 // *ptiles to the partials per (slice, validator).
-template <int VARIANT, int R, int NW = 8>
+// The strip scan runs 8 waves per 16-miner strip. Fewer waves with more
+// rows per lane (a cheaper per-epoch column reduction) lose: c2 YumaRust
+// bonds 3.50 -> 5.11 ms with 4 waves, 9.12 with 2 (profiles/r05/ab_cn_waves.txt)
+template <int VARIANT, int R>
 int launch_cn(hipStream_t st, yk::BondArgs& A, int* ptiles) {
   A.rowblocks = 1;
   A.cblocks = (A.M + yk::kCnStrip - 1) / yk::kCnStrip;
   *ptiles = A.cblocks;
   const long long nblocks = (long long)A.N * A.cblocks;
-  constexpr int P = NW == 8 ? (R <= 2 ? 4 : (R == 4 ? 2 : 1)) : (R <= 4 ? 3 : 2);
-  if (A.rq4 != nullptr)  // k_rowsum's screened reciprocals (run_impl; not the shard stages)
-    YK_LAUNCH((yk::k_bonds_cn<VARIANT, R, P, NW, true>), nblocks, 64 * NW, st, A);
-  else
-    YK_LAUNCH((yk::k_bonds_cn<VARIANT, R, P, NW, false>), nblocks, 64 * NW, st, A);
+  constexpr int P = R <= 2 ? 4 : (R == 4 ? 2 : 1);  // epochs in flight
+  // RQ: k_rowsum's screened reciprocals (run_impl; not the shard stages)
+  with_bool(A.rq4 != nullptr, [&](auto RQ) {
+    YK_LAUNCH((yk::k_bonds_cn<VARIANT, R, P, 8, decltype(RQ)::value>), nblocks, 512, st, A);
+  });
   return yk::DP_TV;
 }
-// YumaRust's strip scan: 8 waves per 16-miner strip. Fewer waves with more
-// rows per lane (a cheaper per-epoch column reduction) lose: c2 YumaRust
-// bonds 3.50 -> 5.11 ms with 4 waves, 9.12 with 2 (profiles/r05/ab_cn_waves.txt)
 template <int VARIANT>
 int launch_cn_rows(hipStream_t st, yk::BondArgs& A, int* ptiles) {
   const int V = A.V;
@@ -5570,18 +5461,19 @@ int launch_bonds_colnorm(RowCfg rc, hipStream_t st, yk::BondArgs& A, int* ptiles
   A.rowblocks = 1;
   A.cblocks = A.tiles;
   const long long nblocks = (long long)A.N * A.tiles;
+  auto go = [&](auto kern, int nt) { YK_LAUNCH(kern, nblocks, nt, st, A); };
   switch (rc) {
     case RC_256_1:
-      YK_LAUNCH((yk::k_bonds<VARIANT, 256, 1, VEC>), nblocks, 256, st, A);
+      go(yk::k_bonds<VARIANT, 256, 1, VEC>, 256);
       break;
     case RC_256_4:
-      YK_LAUNCH((yk::k_bonds<VARIANT, 256, 4, VEC>), nblocks, 256, st, A);
+      go(yk::k_bonds<VARIANT, 256, 4, VEC>, 256);
       break;
     case RC_256_16:
-      YK_LAUNCH((yk::k_bonds<VARIANT, 256, 16, VEC>), nblocks, 256, st, A);
+      go(yk::k_bonds<VARIANT, 256, 16, VEC>, 256);
       break;
     case RC_1024_16:
-      YK_LAUNCH((yk::k_bonds<VARIANT, 1024, 16, VEC>), nblocks, 1024, st, A);
+      go(yk::k_bonds<VARIANT, 1024, 16, VEC>, 1024);
       break;
   }
   return yk::DP_TV;
@@ -5632,10 +5524,10 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
   if constexpr (VEC) {
     if (hist && A.M >= 1024) {
       constexpr int P = VARIANT <= YUMA_VARIANT_YUMA2 ? kWidePCn : kWideP;
-      if constexpr (kElemRq(VARIANT, true)) {
-        if (A.rq4 != nullptr) return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, true>(st, A);
-      }
-      return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ>(st, A);
+      return with_bool(kElemRq(VARIANT, true) && A.rq4 != nullptr, [&](auto RQ) {
+        constexpr bool kRq = kElemRq(VARIANT, true) && decltype(RQ)::value;
+        return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, kRq>(st, A);
+      });
     }
   }
   if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float>) {
@@ -5644,10 +5536,9 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
       A.rowblocks = (A.V + 16 * R - 1) / (16 * R);
       A.cblocks = A.tiles;
       const long long nblocks = (long long)((A.N + K - 1) / K) * A.rowblocks * A.tiles;
-      if (hist)
-        YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, true>), nblocks, 256, st, A);
-      else
-        YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, false>), nblocks, 256, st, A);
+      with_bool(hist, [&](auto HIST) {
+        YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, decltype(HIST)::value>), nblocks, 256, st, A);
+      });
       return yk::DP_TV;
     }
   }
@@ -5656,19 +5547,17 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
     // flight) once the grid has blocks to spare: c4 1.41 -> 1.38 ms; with
     // c2's 512 such blocks 0.99 -> 1.31, so one row per lane there
     const long long blocks_r2 = (long long)A.N * ((A.V + 7) / 8) * ((A.M + 255) / 256);
-    if constexpr (VEC && kElemRq(VARIANT, false)) {
-      if (A.rq4 != nullptr) {
-        if (blocks_r2 >= 4096)
-          return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, true>(st, A);
-        return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, true>(st, A);
-      }
-    }
-    if (blocks_r2 >= 4096)
-      return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE>(st, A);
-    return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE>(st, A);
+    constexpr bool kRqOk = VEC && kElemRq(VARIANT, false);
+    return with_bool(kRqOk && A.rq4 != nullptr, [&](auto RQ) {
+      constexpr bool kRq = kRqOk && decltype(RQ)::value;
+      if (blocks_r2 >= 4096)
+        return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, kRq>(st, A);
+      return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, kRq>(st, A);
+    });
   }
-  if (hist) return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, true, 256, 64, yk::DP_TV>(st, A);
-  return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, false, 256, 64, yk::DP_TV>(st, A);
+  return with_bool(hist, [&](auto HIST) {  // the history goes out with non-temporal stores
+    return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, decltype(HIST)::value, 256, 64, yk::DP_TV>(st, A);
+  });
 }
 
 // Launch the bond scan for A.N scenarios over epochs [A.t0, A.t1); returns
@@ -5724,6 +5613,98 @@ bool u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* o
   return true;
 }
 
+// What run_impl and shard_stage_impl decide alike.
+int check_sizes(int variant, int N, int E, int V, int M) {
+  if (variant < 0 || variant > 4) return fail(YUMA_EINVAL, "unknown variant %d", variant);
+  if (N < 1 || E < 1 || V < 1 || M < 1)
+    return fail(YUMA_EINVAL, "sizes must be positive (N=%d E=%d V=%d M=%d)", N, E, V, M);
+  if (V > YUMA_MAX_VALIDATORS)
+    return fail(YUMA_EUNSUPPORTED, "V=%d exceeds YUMA_MAX_VALIDATORS=%d", V,
+                YUMA_MAX_VALIDATORS);
+  return YUMA_OK;
+}
+
+// Vector form: a lane's 4 columns are one vector load (16 bytes of fp32, 8 of
+// uint16) of W and of every fp32 matrix read or written
+template <typename WT>
+bool vector_form(int M, const WT* W, const float* B_init, const float* Wprev_init, const yuma_outputs_t* out) {
+  if ((M % 4) != 0 || ((uintptr_t)W & (4 * sizeof(WT) - 1)) != 0) return false;
+  const float* mats[] = {B_init, Wprev_init, out->Wn, out->Wc, out->Wb, out->B_inst,
+                         out->B_hist, out->B_final};
+  for (const float* p : mats)
+    if (p != nullptr && !aligned16(p)) return false;
+  return true;
+}
+
+// Per-slice vectors and the bond state: the caller's output where requested,
+// else the workspace's. (Liquid bond_alpha: scenarios with liquid_mode OFF
+// neither write nor read it.)
+struct Bufs {
+  float *C, *I, *R, *Bstate, *ba;
+};
+Bufs pick_bufs(const yuma_outputs_t* out, const Workspace& ws) {
+  return {out->C ? out->C : ws.C, out->I ? out->I : ws.I, out->R ? out->R : ws.R,
+          out->B_final ? out->B_final : ws.Bstate, out->bond_alpha ? out->bond_alpha : ws.ba};
+}
+
+// Yuma / Yuma2 (the workspace has csb): does the rank pass form the bond
+// column sums Σ_v S·W_b, so that the bond scan is element-wise? Above kRegRows
+// validators always (the element-wise scan is the only one there, and it
+// writes W_b / B_inst itself); else for run outputs above 64 validators, with
+// no matrix of the full outputs asked for (ws.tvc: T_v).
+bool forms_csb(const Workspace& ws, int V, const yuma_outputs_t* out) {
+  if (ws.csb == nullptr) return false;
+  if (V > yk::kRegRows) return true;
+  return V > 64 && out->Wn == nullptr && out->Wc == nullptr && ws.tvc == nullptr && out->Wb == nullptr &&
+         out->B_inst == nullptr;
+}
+
+// The bond scan's arguments over every epoch of a run, without shared inputs,
+// screened reciprocals (rq4) or rank classes (csrep): callers set what differs.
+yk::BondArgs bond_args(const float* W, const Workspace& ws, const Bufs& b, const yuma_params_t* prm,
+                       const float* B_init, const float* Wprev_init, const yuma_outputs_t* out, float* csb,
+                       int N, int E, int V, int M) {
+  yk::BondArgs A{};
+  A.W = W;
+  A.rsd = ws.rsd;
+  A.sn = ws.sn;
+  A.C = b.C;
+  A.I = b.I;
+  A.ba = b.ba;
+  A.prm = prm;
+  A.B_init = B_init;
+  A.Wprev_init = Wprev_init;
+  A.Bstate = b.Bstate;
+  A.B_hist = out->B_hist;
+  A.Wb_out = out->Wb;
+  A.Binst_out = out->B_inst;
+  A.dpart = ws.dpart;
+  A.csb = csb;
+  A.csr = ws.csr;
+  A.R = b.R;
+  A.cpart = ws.cpart;
+  A.N = N;
+  A.V = V;
+  A.M = M;
+  A.tiles = (M + yk::kTileM - 1) / yk::kTileM;
+  A.t0 = 0;
+  A.t1 = E;
+  A.ep = dte_stride(E);
+  return A;
+}
+
+// D / Dn (and T_v) of ns slices from the dividend partials in layout dpl
+void launch_finalize(hipStream_t st, long long ns, const float* dsrc, const Workspace& ws, int variant, int V,
+                     long long s0, int ptiles, const float* tvc, const float* tvn, const yuma_outputs_t* out,
+                     int dpl, int tiles) {
+  if (V > yk::kRegRows)
+    YK_LAUNCH(yk::k_finalize_big, ns, 256, st, dsrc, ws.sn, variant, V, s0, ptiles, tvc, tvn, out->Dn, out->D,
+              out->Tv, dpl, tiles, ws.dsum);
+  else
+    YK_LAUNCH(yk::k_finalize, ns, 256, st, dsrc, ws.sn, variant, V, s0, ptiles, tvc, tvn, out->Dn, out->D,
+              out->Tv, dpl, tiles);
+}
+
 // WT: the element type of W, float or (YUMA_RUN_W_U16) uint16_t. Element w of
 // a uint16 W is the weight (float)w; slices and rows are indexed in elements.
 template <typename WT>
@@ -5733,12 +5714,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
              void* stream, float* phase_ms = nullptr, int wsh = 0) {
   constexpr bool U16 = std::is_same_v<WT, uint16_t>;
   static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
-  if (variant < 0 || variant > 4) return fail(YUMA_EINVAL, "unknown variant %d", variant);
-  if (N < 1 || E < 1 || V < 1 || M < 1)
-    return fail(YUMA_EINVAL, "sizes must be positive (N=%d E=%d V=%d M=%d)", N, E, V, M);
-  if (V > YUMA_MAX_VALIDATORS)
-    return fail(YUMA_EUNSUPPORTED, "V=%d exceeds YUMA_MAX_VALIDATORS=%d", V,
-                YUMA_MAX_VALIDATORS);
+  if (const int err = check_sizes(variant, N, E, V, M)) return err;
   if ((M + yk::kTileM - 1) / yk::kTileM > yk::kMaxTiles) return fail(YUMA_EINVAL, "M too large");
   if (!prm || !W || !S || !out || !workspace)
     return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
@@ -5753,12 +5729,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
   const int tiles = (M + yk::kTileM - 1) / yk::kTileM;
   const RowCfg rc = row_cfg(V);
 
-  // a lane's 4 columns are one vector load: 16 bytes of fp32, 8 of uint16
-  bool vec = (M % 4) == 0 && ((uintptr_t)W & (4 * sizeof(WT) - 1)) == 0;
-  const float* mats[] = {B_init, Wprev_init, out->Wn, out->Wc, out->Wb, out->B_inst,
-                         out->B_hist, out->B_final};
-  for (const float* p : mats)
-    if (p != nullptr && !aligned16(p)) vec = false;
+  const bool vec = vector_form(M, W, B_init, Wprev_init, out);
   if constexpr (U16) {  // before the first launch
     if (!u16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
       return fail(YUMA_EUNSUPPORTED,
@@ -5770,13 +5741,16 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
                   "YUMA_RUN_W_U16 needs W 8-byte aligned and the fp32 matrices 16-byte aligned");
   }
 
-  float* C = out->C ? out->C : ws.C;
-  float* I = out->I ? out->I : ws.I;
-  float* Rr = out->R ? out->R : ws.R;
-  float* Bstate = out->B_final ? out->B_final : ws.Bstate;
-  // liquid bond_alpha lives in the caller's buffer when requested; scenarios
-  // with liquid_mode OFF neither write nor read it
-  float* ba_buf = out->bond_alpha ? out->bond_alpha : ws.ba;
+  // VEC as a template argument; uint16 runs are vector form only (checked above)
+  auto with_vec = [&](auto f) {
+    if constexpr (U16)
+      return f(std::true_type{});
+    else
+      return with_bool(vec, f);
+  };
+
+  const Bufs buf = pick_bufs(out, ws);
+  float *const C = buf.C, *const I = buf.I, *const Rr = buf.R, *const ba_buf = buf.ba;
 
   // one chunk by default: phase 1 of every epoch, then one bond scan
   if (chunk <= 0 || chunk > E) chunk = E;
@@ -5796,14 +5770,8 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
   // one load of the tile (k_consensus_mc; wave-owned columns, <= 256 validators)
   const bool mc = crep != nullptr && V <= 256;
   if (mc) YK_LAUNCH(yk::k_class_list, 1, 256, st, ws.crep, N, ws.clist);
-  // Yuma / Yuma2 run outputs above 64 validators: the streaming rank also
-  // forms the bond column sums Σ_v S·W_b and the bond scan is element-wise
   const bool streaming = out->Wn == nullptr && out->Wc == nullptr && ws.tvc == nullptr;
-  // (above kRegRows validators always: the element-wise scan is the only
-  // Yuma / Yuma2 bond scan there, and it writes W_b / B_inst itself)
-  float* csb = (ws.csb != nullptr &&
-                (V > yk::kRegRows || (streaming && V > 64 && out->Wb == nullptr && out->B_inst == nullptr)))
-                   ? ws.csb : nullptr;
+  float* csb = forms_csb(ws, V, out) ? ws.csb : nullptr;
   const bool rank_stream = streaming && variant != YUMA_VARIANT_YUMA2;  // Yuma2's W_prev: rank per scenario
   const int* rcrep = rank_stream ? crep : nullptr;
   if (rcrep != nullptr && csb != nullptr) {  // the column sums depend on bond_penalty too
@@ -5827,44 +5795,28 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
       const int nchunks = (M + 255) / 256;
       const bool wide = nchunks >= yk::kWideChunks && nchunks <= yk::kMaxWideChunks;
       tm.mark(YUMA_PHASE_ROWSUM);
-      if constexpr (U16) {  // vec holds
-        if (wide)
-          YK_LAUNCH((yk::k_rowsum<true, true, WT>), rs_in * V, 256, st, W, S, V, M, rs_s0, V, ws.rsd,
-                    ws.sn, 0, ws.sx, fan, ws.rq4);
-        else
-          YK_LAUNCH((yk::k_rowsum<true, false, WT>), rs_in * rowblocks4, 256, st, W, S, V, M, rs_s0,
-                    rowblocks4, ws.rsd, ws.sn, 0, ws.sx, fan, ws.rq4);
-      } else if (wide && vec)
-        YK_LAUNCH((yk::k_rowsum<true, true>), rs_in * V, 256, st, W, S, V, M, rs_s0, V, ws.rsd,
-                  ws.sn, 0, ws.sx, fan, ws.rq4);
-      else if (wide)
-        YK_LAUNCH((yk::k_rowsum<false, true>), rs_in * V, 256, st, W, S, V, M, rs_s0, V, ws.rsd,
-                  ws.sn, 0, ws.sx, fan, ws.rq4);
-      else if (vec)
-        YK_LAUNCH(yk::k_rowsum<true>, rs_in * rowblocks4, 256, st, W, S, V, M, rs_s0, rowblocks4,
-                  ws.rsd, ws.sn, 0, ws.sx, fan, ws.rq4);
-      else
-        YK_LAUNCH(yk::k_rowsum<false>, rs_in * rowblocks4, 256, st, W, S, V, M, rs_s0,
-                  rowblocks4, ws.rsd, ws.sn, 0, ws.sx, fan, ws.rq4);
+      with_vec([&](auto VEC) {
+        with_bool(wide, [&](auto WIDE) {  // a block per row, or per 4 rows
+          const int rb = wide ? V : rowblocks4;
+          YK_LAUNCH((yk::k_rowsum<decltype(VEC)::value, decltype(WIDE)::value, WT>), rs_in * rb, 256, st, W, S, V,
+                    M, rs_s0, rb, ws.rsd, ws.sn, 0, ws.sx, fan, ws.rq4);
+        });
+      });
       tm.mark(YUMA_PHASE_CONSENSUS);
-      if constexpr (U16) {
-        launch_consensus<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, s0, tiles,
-                               ws.craw, out->P, wsh, crep, ws.rq4);
-      } else if (mc) {
-        const int G = N < yk::kMcGroups ? N : yk::kMcGroups;
-        const long long nb = (long long)(c1 - c0) * tiles * G;
-        if (vec)
-          launch_consensus_mc<true>(rc, nb, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, c0, tiles, ws.craw,
-                                    ws.clist, G);
-        else
-          launch_consensus_mc<false>(rc, nb, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, c0, tiles, ws.craw,
-                                     ws.clist, G);
-      } else if (vec)
-        launch_consensus<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, s0, tiles,
-                               ws.craw, out->P, wsh, crep, ws.rq4);
-      else
-        launch_consensus<false>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, s0,
-                                tiles, ws.craw, out->P, wsh, crep);
+      with_vec([&](auto VEC) {
+        constexpr bool kVec = decltype(VEC)::value;
+        if constexpr (!U16) {
+          if (mc) {
+            const int G = N < yk::kMcGroups ? N : yk::kMcGroups;
+            const long long nb = (long long)(c1 - c0) * tiles * G;
+            launch_consensus_mc<kVec>(rc, nb, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, c0, tiles, ws.craw,
+                                      ws.clist, G);
+            return;
+          }
+        }
+        launch_consensus<kVec>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, s0, tiles, ws.craw,
+                               out->P, wsh, crep, kVec ? ws.rq4 : nullptr);
+      });
       tm.mark(YUMA_PHASE_QUANTISE);
       YK_LAUNCH(yk::k_quantise<256>, ns, 256, st, ws.craw, prm, variant, N, M, s0, C, ws.qlev,
                 ba_buf, ws.scal, nullptr, nullptr, 0, crep);
@@ -5875,14 +5827,12 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
       const int* rlist = (mc && rcrep == crep && csb == nullptr && M < 16384) ? ws.clist : nullptr;
       if constexpr (U16)
         launch_rank<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, N, V, M, s0, tiles, Rr, ws.rpart);
-      else if (vec)
-        launch_rank<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
-                          variant == YUMA_VARIANT_YUMA2, N, V, M, s0, tiles, Rr, ws.rpart, out->Wn,
-                          out->Wc, ws.tvc, ws.tvn, wsh, rcrep, csb, ws.csr, prm, rlist);
       else
-        launch_rank<false>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
-                           variant == YUMA_VARIANT_YUMA2, N, V, M, s0, tiles, Rr, ws.rpart,
-                           out->Wn, out->Wc, ws.tvc, ws.tvn, wsh, rcrep, csb, ws.csr, prm, rlist);
+        with_bool(vec, [&](auto VEC) {
+          launch_rank<decltype(VEC)::value>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
+                                            variant == YUMA_VARIANT_YUMA2, N, V, M, s0, tiles, Rr, ws.rpart,
+                                            out->Wn, out->Wc, ws.tvc, ws.tvn, wsh, rcrep, csb, ws.csr, prm, rlist);
+        });
     }
     tm.mark(YUMA_PHASE_INCENTIVE);
     const int ich = (M + yk::kIncCols - 1) / yk::kIncCols;
@@ -5890,35 +5840,14 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
               out->P ? out->T : nullptr, ws.scal, nullptr, rcrep, N, ich, incentive_v4(M, Rr, I, out),
               (out->R != nullptr || variant == YUMA_VARIANT_RUST) ? 1 : 0);
 
-    yk::BondArgs A{};
-    A.W = reinterpret_cast<const float*>(W);  // the scan is launched for WT
-    A.rsd = ws.rsd;
-    A.sn = ws.sn;
-    A.C = C;
-    A.I = I;
-    A.ba = ba_buf;
-    A.prm = prm;
-    A.B_init = B_init;
-    A.Wprev_init = Wprev_init;
-    A.Bstate = Bstate;
-    A.B_hist = out->B_hist;
-    A.Wb_out = out->Wb;
-    A.Binst_out = out->B_inst;
-    A.dpart = ws.dpart;
+    // (A.W: the scan is launched for WT)
+    yk::BondArgs A = bond_args(reinterpret_cast<const float*>(W), ws, buf, prm, B_init, Wprev_init, out, csb, N,
+                               E, V, M);
     A.rq4 = ws.rq4;
-    A.csb = csb;
-    A.csr = ws.csr;
     A.csrep = csb != nullptr ? rcrep : nullptr;
-    A.R = Rr;
-    A.cpart = ws.cpart;
-    A.N = N;
-    A.V = V;
-    A.M = M;
-    A.tiles = tiles;
     A.t0 = c0;
     A.t1 = c1;
     A.wsh = wsh;
-    A.ep = dte_stride(E);
     tm.mark(YUMA_PHASE_BONDS);
     int ptiles = tiles;
     int dpl;
@@ -5926,8 +5855,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
       dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem<YUMA_VARIANT_YUMA3, true, WT>(st, A)
                                           : launch_bonds_elem<YUMA_VARIANT_YUMA4, true, WT>(st, A);
     else
-      dpl = vec ? launch_bonds<true>(variant, rc, st, A, &ptiles)
-                : launch_bonds<false>(variant, rc, st, A, &ptiles);
+      dpl = with_bool(vec, [&](auto VEC) { return launch_bonds<decltype(VEC)::value>(variant, rc, st, A, &ptiles); });
     tm.mark(YUMA_PHASE_FINALIZE);
     const float* dsrc = ws.dpart;
     if (dpl == yk::DP_QTE) {
@@ -5936,12 +5864,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
       dsrc = ws.dsum;
       dpl = yk::DP_PRE;
     }
-    if (V > yk::kRegRows)
-      YK_LAUNCH(yk::k_finalize_big, ns, 256, st, dsrc, ws.sn, variant, V, s0, ptiles, ws.tvc, ws.tvn, out->Dn,
-                out->D, out->Tv, dpl, tiles, ws.dsum);
-    else
-      YK_LAUNCH(yk::k_finalize, ns, 256, st, dsrc, ws.sn, variant, V, s0, ptiles, ws.tvc,
-                ws.tvn, out->Dn, out->D, out->Tv, dpl, tiles);
+    launch_finalize(st, ns, dsrc, ws, variant, V, s0, ptiles, ws.tvc, ws.tvn, out, dpl, tiles);
     if (out->Sn != nullptr)
       (void)hipMemcpyAsync(out->Sn + s0 * V, ws.sn + s0 * V, (size_t)ns * V * 4,
                            hipMemcpyDeviceToDevice, st);
@@ -5976,13 +5899,8 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
                      const float* W, const float* S, const float* B_init,
                      const float* Wprev_init, const yuma_shard_io_t* io,
                      const yuma_outputs_t* out, void* workspace, size_t ws_bytes, void* stream) {
-  if (variant < 0 || variant > 4) return fail(YUMA_EINVAL, "unknown variant %d", variant);
   if (stage < 1 || stage > 5) return fail(YUMA_EINVAL, "unknown shard stage %d", stage);
-  if (N < 1 || E < 1 || V < 1 || M < 1)
-    return fail(YUMA_EINVAL, "sizes must be positive (N=%d E=%d V=%d M=%d)", N, E, V, M);
-  if (V > YUMA_MAX_VALIDATORS)
-    return fail(YUMA_EUNSUPPORTED, "V=%d exceeds YUMA_MAX_VALIDATORS=%d", V,
-                YUMA_MAX_VALIDATORS);
+  if (const int err = check_sizes(variant, N, E, V, M)) return err;
   if (!prm || !W || !S || !out || !io || !workspace)
     return fail(YUMA_EINVAL, "null params/W/S/io/outputs/workspace");
   if (io->M_total < M || io->col0 < 0 || io->col0 + M > io->M_total)
@@ -5999,34 +5917,22 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
   const int tiles = (M + yk::kTileM - 1) / yk::kTileM;
   const RowCfg rc = row_cfg(V);
   const bool rust = variant == YUMA_VARIANT_RUST;
-  bool vec = (M % 4) == 0 && aligned16(W);
-  const float* mats[] = {B_init, Wprev_init, out->Wn, out->Wc, out->Wb, out->B_inst,
-                         out->B_hist, out->B_final};
-  for (const float* p : mats)
-    if (p != nullptr && !aligned16(p)) vec = false;
-  float* C = out->C ? out->C : ws.C;
-  float* I = out->I ? out->I : ws.I;
-  float* R = out->R ? out->R : ws.R;
-  float* Bstate = out->B_final ? out->B_final : ws.Bstate;
-  float* ba_buf = out->bond_alpha ? out->bond_alpha : ws.ba;
+  const bool vec = vector_form(M, W, B_init, Wprev_init, out);
+  const Bufs buf = pick_bufs(out, ws);
+  float *const C = buf.C, *const I = buf.I, *const R = buf.R, *const ba_buf = buf.ba;
   int* qlev = io->levels ? io->levels : ws.qlev;
   const long long ns = (long long)E * N;
   // Yuma / Yuma2: the bond column sums are sums over validators, local to
   // the shard's columns: formed by stage 3's rank pass, read by stage 4's scan
-  float* shard_csb = (ws.csb != nullptr &&
-                      (V > yk::kRegRows || (!full && V > 64 && out->Wn == nullptr && out->Wc == nullptr &&
-                                            out->Wb == nullptr && out->B_inst == nullptr)))
-                         ? ws.csb : nullptr;
+  float* shard_csb = forms_csb(ws, V, out) ? ws.csb : nullptr;
   switch (stage) {
     case 1: {
       if (!io->rowsum_part) return fail(YUMA_EINVAL, "stage 1 needs io->rowsum_part");
       const int rb4 = (V + 3) / 4;
-      if (vec)
-        YK_LAUNCH(yk::k_rowsum<true>, ns * rb4, 256, st, W, S, V, M, 0LL, rb4, io->rowsum_part,
+      with_bool(vec, [&](auto VEC) {
+        YK_LAUNCH(yk::k_rowsum<decltype(VEC)::value>, ns * rb4, 256, st, W, S, V, M, 0LL, rb4, io->rowsum_part,
                   ws.sn, 1, ws.sx, 1, (float4*)nullptr);
-      else
-        YK_LAUNCH(yk::k_rowsum<false>, ns * rb4, 256, st, W, S, V, M, 0LL, rb4, io->rowsum_part,
-                  ws.sn, 1, ws.sx, 1, (float4*)nullptr);
+      });
       break;
     }
     case 2: {
@@ -6035,12 +5941,10 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
       long long nb = (ns * V + 255) / 256;
       if (nb > 4096) nb = 4096;
       YK_LAUNCH(yk::k_add_eps, nb, 256, st, io->rowsum, ns * V, ws.rsd);
-      if (vec)
-        launch_consensus<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, 0LL, tiles,
-                               ws.craw, out->P, 0, nullptr);
-      else
-        launch_consensus<false>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, 0LL, tiles,
-                                ws.craw, out->P, 0, nullptr);
+      with_bool(vec, [&](auto VEC) {
+        launch_consensus<decltype(VEC)::value>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, 0LL,
+                                               tiles, ws.craw, out->P, 0, nullptr);
+      });
       YK_LAUNCH(yk::k_csum, ns, 256, st, ws.craw, rust ? 1 : 0, M, io->csum_part, io->csum_part_d);
       break;
     }
@@ -6050,14 +5954,11 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
       if (full && !io->tv_part) return fail(YUMA_EINVAL, "stage 3 with out->Tv needs io->tv_part");
       YK_LAUNCH(yk::k_quantise<256>, ns, 256, st, ws.craw, prm, variant, N, M, 0LL, C, qlev,
                 ba_buf, ws.scal, rust ? nullptr : io->csum, rust ? io->csum_d : nullptr, 1, nullptr);
-      if (vec)
-        launch_rank<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
-                          variant == YUMA_VARIANT_YUMA2, N, V, M, 0LL, tiles, R, ws.rpart,
-                          out->Wn, out->Wc, ws.tvc, ws.tvn, 0, nullptr, shard_csb, ws.csr, prm);
-      else
-        launch_rank<false>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
-                           variant == YUMA_VARIANT_YUMA2, N, V, M, 0LL, tiles, R, ws.rpart,
-                           out->Wn, out->Wc, ws.tvc, ws.tvn, 0, nullptr, shard_csb, ws.csr, prm);
+      with_bool(vec, [&](auto VEC) {
+        launch_rank<decltype(VEC)::value>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
+                                          variant == YUMA_VARIANT_YUMA2, N, V, M, 0LL, tiles, R, ws.rpart, out->Wn,
+                                          out->Wc, ws.tvc, ws.tvn, 0, nullptr, shard_csb, ws.csr, prm);
+      });
       YK_LAUNCH(yk::k_rsum, ns, 64, st, ws.rpart, tiles, io->rsum_part);
       if (full) {
         YK_LAUNCH(yk::k_dsum, ns, 256, st, ws.tvc, V, tiles, io->tv_part);
@@ -6076,35 +5977,10 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
       const int ich = (M + yk::kIncCols - 1) / yk::kIncCols;
       YK_LAUNCH(yk::k_incentive, ns * ich, 256, st, R, ws.rpart, out->P, M, 0LL, tiles, I,
                 out->P ? out->T : nullptr, ws.scal, io->rsum, nullptr, N, ich, incentive_v4(M, R, I, out), 1);
-      yk::BondArgs A{};
-      A.W = W;
-      A.rsd = ws.rsd;
-      A.sn = ws.sn;
-      A.C = C;
-      A.I = I;
-      A.ba = ba_buf;
-      A.prm = prm;
-      A.B_init = B_init;
-      A.Wprev_init = Wprev_init;
-      A.Bstate = Bstate;
-      A.B_hist = out->B_hist;
-      A.Wb_out = out->Wb;
-      A.Binst_out = out->B_inst;
-      A.dpart = ws.dpart;
-      A.csb = shard_csb;
-      A.csr = ws.csr;
-      A.R = R;
-      A.cpart = ws.cpart;
-      A.N = N;
-      A.V = V;
-      A.M = M;
-      A.tiles = tiles;
-      A.t0 = 0;
-      A.t1 = E;
-      A.ep = dte_stride(E);
+      yk::BondArgs A = bond_args(W, ws, buf, prm, B_init, Wprev_init, out, shard_csb, N, E, V, M);
       int ptiles = tiles;
-      const int dpl = vec ? launch_bonds<true>(variant, rc, st, A, &ptiles)
-                          : launch_bonds<false>(variant, rc, st, A, &ptiles);
+      const int dpl =
+          with_bool(vec, [&](auto VEC) { return launch_bonds<decltype(VEC)::value>(variant, rc, st, A, &ptiles); });
       if (dpl == yk::DP_QTE)
         YK_LAUNCH(yk::k_dte_sum, (long long)N * ((E + 15) / 16) * ((V + 3) / 4), 256, st, ws.dpart, N, V,
                   ptiles, A.ep, 0, E, io->dsum_part);
@@ -6115,14 +5991,8 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
     case 5: {
       if (!io->dsum) return fail(YUMA_EINVAL, "stage 5 needs io->dsum");
       if (full && !io->tv) return fail(YUMA_EINVAL, "stage 5 with out->Tv needs io->tv");
-      if (V > yk::kRegRows)
-        YK_LAUNCH(yk::k_finalize_big, ns, 256, st, io->dsum, ws.sn, variant, V, 0LL, 1,
-                  full ? io->tv : nullptr, full ? io->tv + ns * V : nullptr, out->Dn, out->D, out->Tv,
-                  (int)yk::DP_TV, 1, ws.dsum);
-      else
-        YK_LAUNCH(yk::k_finalize, ns, 256, st, io->dsum, ws.sn, variant, V, 0LL, 1,
-                  full ? io->tv : nullptr, full ? io->tv + ns * V : nullptr, out->Dn, out->D,
-                  out->Tv, (int)yk::DP_TV, 1);
+      launch_finalize(st, ns, io->dsum, ws, variant, V, 0LL, 1, full ? io->tv : nullptr,
+                      full ? io->tv + ns * V : nullptr, out, yk::DP_TV, 1);
       if (out->Sn != nullptr)
         (void)hipMemcpyAsync(out->Sn, ws.sn, (size_t)ns * V * 4, hipMemcpyDeviceToDevice, st);
       if (out->alpha_ab != nullptr)
