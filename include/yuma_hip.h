@@ -120,7 +120,8 @@ typedef struct yuma_outputs {
   float* Wc;         /* [E][N][V][M] consensus_clipped_weight                    */
   float* Wb;         /* [E][N][V][M] weight_for_bond (Yuma1/Yuma2)               */
   float* B_inst;     /* [E][N][V][M] validator_bond (Rust/Yuma1/Yuma2)           */
-  float* B_hist;     /* [E][N][V][M] bond state after each epoch (bonds_per_epoch) */
+  float* B_hist;     /* [E][N][V][M] bond state after each epoch (bonds_per_epoch);
+                        [n_hist][N][V][M] under a history stride (yuma_run_opts)   */
   float* B_final;    /* [N][V][M]    bond state after the last epoch             */
 } yuma_outputs_t;
 
@@ -180,6 +181,41 @@ int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int 
                 const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                 int chunk_epochs, int flags, void* stream, float* phase_ms);
 
+/* yuma_run_ex with an options record: its flags, and a stride for the bond
+ * history. With hist_stride = s (0 counts as 1) and hist_first = f the run
+ * stores the bond state after the epochs t_j = f + j*s < E only, counted from
+ * the run's epoch 0 whatever chunk_epochs is: out->B_hist is
+ * [n_hist][N][V][M] with n_hist = yuma_hist_slots(E, s, f), and slot j holds
+ * the bits the dense history holds at epoch t_j (resets applied as there).
+ * Every other output, B_final included, is that of the dense run. f lets a run
+ * resumed from B_final keep the phase of the run it continues. s <= 1 with
+ * f = 0 is the dense history on yuma_run_ex's own path. f >= E stores nothing.
+ * The history costs n_hist / E of the dense history's memory and write
+ * traffic; the stored epochs still go out as whole 16-byte row-contiguous
+ * stores, the others skip the store on a block-uniform test of the epoch. On
+ * MI355X at 256 x 4096, 1000 epochs, the dense history is 4.19 GB of the bond
+ * scan's 8.5 GB of traffic (measured effect: README.md, profiles/hist_stride/).
+ * Combines with YUMA_RUN_SHARED_INPUTS and YUMA_RUN_W_U16 as the dense
+ * history does. opts NULL: every default. hist_stride < 0, hist_first < 0, an
+ * unknown flag or a non-zero reserved word return YUMA_EINVAL before the first
+ * launch. The workspace size does not depend on the options.
+ * yuma_epoch and yuma_shard_stage (the wide-subnet path) keep the dense
+ * history only.                                                              */
+typedef struct yuma_run_options {
+  int32_t flags;        /* yuma_run_flags                                       */
+  int32_t hist_stride;  /* 0 or 1: every epoch                                  */
+  int32_t hist_first;   /* first stored epoch                                   */
+  int32_t reserved[5];  /* must be 0                                            */
+} yuma_run_options_t;   /* 32 bytes */
+int yuma_run_opts(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
+                  const float* W, const float* S, const float* B_init, const float* Wprev_init,
+                  const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
+                  int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms);
+/* Slots of the bond history of an E-epoch run under these options:
+ * hist_first < E ? (E - 1 - hist_first) / stride + 1 : 0 (stride 0 counts as
+ * 1). Host only, needs no GPU. YUMA_EINVAL for E < 1 or a negative argument. */
+int yuma_hist_slots(int E, int hist_stride, int hist_first);
+
 /* 1 when yuma_run_ex / yuma_graph_create_ex with these arguments and
  * YUMA_RUN_W_U16 (`flags`: the run's other flags) read uint16 weights
  * natively, else 0. Host only, needs no GPU; of `out` it reads only which
@@ -209,6 +245,12 @@ int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* 
                          int E, int V, int M, const float* W, const float* S,
                          const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                          void* workspace, size_t workspace_bytes, int chunk_epochs, int flags);
+/* yuma_graph_create with yuma_run_opts's options (the history stride). */
+int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                           int E, int V, int M, const float* W, const float* S,
+                           const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                           void* workspace, size_t workspace_bytes, int chunk_epochs,
+                           const yuma_run_options_t* opts);
 /* Replay on `stream` (stream-ordered, no host synchronisation). */
 int yuma_graph_launch(yuma_graph_t graph, void* stream);
 /* Kernel nodes in the captured graph (diagnostics / tests). */

@@ -3234,7 +3234,19 @@ struct BondArgs {
   int wsh;      // every scenario reads input slice t (yuma_run_shared)
   int cblocks;  // k_bonds_elem: column blocks of CB miners per row block
   int ep;       // DP_QTE: epoch stride of a (scenario, quad, row) series (multiple of 16)
+  // Strided bond history (yuma_run_opts: stride s, first stored epoch f): the
+  // state after epoch f + j s goes to slot j of B_hist. The host resolves s and
+  // f per launch into the scan's countdown: hnext = the first stored epoch
+  // >= t0 (-1: none left in the run), hslot = its slot, hstride = the distance
+  // to the one after it (s, capped at E: hnext stays an int). A scan stores
+  // when t == hnext, a block-uniform test of t alone, then steps hnext by
+  // hstride and the slot by one; no epoch takes a modulo. The dense history is
+  // hstride = 1, hnext = hslot = t0 (hist_strided() is false, slot == epoch).
+  int hstride, hnext, hslot;
 };
+__host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
+  return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
+}
 
 // Dividend partials. Each bond scan forms p_k = sum over tile k's columns of
 // B·I per (slice, validator) -- k a 64-miner tile, or the column-normalised
@@ -3274,7 +3286,11 @@ __device__ __forceinline__ bool reset_c_zero(const BondArgs& A, int n, int mode,
   return A.C[((long long)(epoch - 1) * A.N + n) * A.M + index] == 0.0f;
 }
 
-template <int VARIANT, int NT, int R, bool VEC>
+// HS: the strided history (BondArgs::hnext; B_hist is not null). A template
+// parameter in every scan, so that the dense-history and history-less
+// instantiations keep their code (a run-time stride moved these kernels'
+// register allocation: 16-row forms 132 -> 456 spilled VGPRs).
+template <int VARIANT, int NT, int R, bool VEC, bool HS = false>
 __global__ __launch_bounds__(NT) void k_bonds(BondArgs A) {
   static_assert(VARIANT == YUMA_VARIANT_RUST || VARIANT == YUMA_VARIANT_YUMA1 || VARIANT == YUMA_VARIANT_YUMA2,
                 "k_bonds serves the column-normalised variants");
@@ -3356,8 +3372,12 @@ __global__ __launch_bounds__(NT) void k_bonds(BondArgs A) {
     }
   }
 
+  // HS: the history countdown, slot slice hsl takes the state after epoch hnext
+  int hnext = HS ? A.hnext : 0;
+  long long hsl = HS ? (long long)A.hslot * N + n : 0;
   for (int t = A.t0; t < A.t1; ++t) {
     const long long slice = (long long)t * N + n;
+    const bool hst = HS && t == hnext;  // block-uniform, from t alone
     float Ic[4], Cc[4], bac[4], omba[4];
     load4_vec(A.I + slice * M, m, M, Ic);
     load4_vec(A.C + slice * M, m, M, Cc);
@@ -3478,14 +3498,18 @@ __global__ __launch_bounds__(NT) void k_bonds(BondArgs A) {
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const int row = row0 + G * i;
-      if (A.B_hist != nullptr && row < V)
-        store4<VEC>(A.B_hist + slice * VM + (long long)row * M, m, M, B[i]);
+      if ((HS ? hst : A.B_hist != nullptr) && row < V)
+        store4<VEC>(A.B_hist + (HS ? hsl : slice) * VM + (long long)row * M, m, M, B[i]);
       float d = 0.0f;
 #pragma unroll
       for (int c = 0; c < 4; ++c)
         if (m + c < M) d = d + B[i][c] * Ic[c];
       d = sum_row16(d);
       if (L.c4 == 0 && row < V) A.dpart[(slice * A.tiles + tile) * V + row] = d;
+    }
+    if (hst) {
+      hnext += A.hstride;
+      hsl += N;
     }
     __syncthreads();  // red[] reuse across epochs
   }
@@ -3542,7 +3566,7 @@ __device__ __forceinline__ void cn_wave_sums(float (&x)[4], float (*red)[kCnStri
   x[3] = a.w;
 }
 
-template <int VARIANT, int R, int P, int NW = 8, bool RQ = false>
+template <int VARIANT, int R, int P, int NW = 8, bool RQ = false, bool HS = false>
 __global__ __launch_bounds__(64 * NW, 1) void k_bonds_cn(BondArgs A) {
   constexpr bool RUST = VARIANT == YUMA_VARIANT_RUST, YUMA2 = VARIANT == YUMA_VARIANT_YUMA2;
   constexpr int RS = 16 * NW;  // row stride between a lane's rows
@@ -3700,6 +3724,9 @@ __global__ __launch_bounds__(64 * NW, 1) void k_bonds_cn(BondArgs A) {
     tq = t + 1;
   };
 
+  // HS (k_bonds): the history countdown, slot slice hsl takes the state after epoch hnext
+  int hnext = HS ? A.hnext : 0;
+  long long hsl = HS ? (long long)A.hslot * N + n : 0;
   int par = 0;  // LDS buffer of this epoch's first column sum
   for (int tb = A.t0; tb < A.t1; tb += P) {
 #pragma unroll
@@ -3707,6 +3734,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_bonds_cn(BondArgs A) {
       const int t = tb + k;
       if (t >= A.t1) break;
       const long long slice = (long long)t * N + n;
+      const bool hst = HS && t == hnext;  // block-uniform, from t alone
       float bac[4], omba[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -3847,11 +3875,11 @@ __global__ __launch_bounds__(64 * NW, 1) void k_bonds_cn(BondArgs A) {
 #pragma unroll
       for (int i = 0; i < R; ++i) {
         const int row = row0 + RS * i;
-        if (A.B_hist != nullptr && row < V && colok)
+        if ((HS ? hst : A.B_hist != nullptr) && row < V && colok)
           // plain (write-back) stores: the L2 of the XCD merges the paired
           // strips' 64-byte halves of each line (non-temporal stores wrote
           // 1.26x the history: PMC 5.65 -> 4.46 GB per c2 launch, same time)
-          *reinterpret_cast<fvec4*>(A.B_hist + slice * VM + (long long)row * M + m) =
+          *reinterpret_cast<fvec4*>(A.B_hist + (HS ? hsl : slice) * VM + (long long)row * M + m) =
               fvec4{B[i][0], B[i][1], B[i][2], B[i][3]};
         float d = 0.0f;
 #pragma unroll
@@ -3859,6 +3887,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_bonds_cn(BondArgs A) {
         d = colok ? d : 0.0f;
         d = qsum4(d);
         if (cq == 0) dpb[((t - tq) * R + i) * 16 + rr] = d;
+      }
+      if (hst) {
+        hnext += A.hstride;
+        hsl += N;
       }
       if (t - tq == DB - 1 || t == A.t1 - 1) flush_d(t);  // block-uniform
     }
@@ -3976,7 +4008,9 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
     for (int c = 0; c < 4; ++c) e[c] = nan_to_num(e[c] / Z[c], 0.0f);
     if (row < V) {
       store4<VEC>(A.Bstate + n * VM + (long long)row * M, m, M, e);
-      if (A.B_hist != nullptr) store4<VEC>(A.B_hist + slice * VM + (long long)row * M, m, M, e);
+      // (one launch per epoch: the host hands a stored epoch its slot, any other no history)
+      if (A.B_hist != nullptr)
+        store4<VEC>(A.B_hist + ((long long)A.hslot * N + n) * VM + (long long)row * M, m, M, e);
     }
     float d = 0.0f;
 #pragma unroll
@@ -4004,8 +4038,10 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // quads run along a row (CB/4 lanes per row), so a wave instruction moves
 // 4 rows x 256 B (CB = 64) or 1 row x 1 KiB (CB >= 256). The dividend partial
 // of each 64-miner tile is the 16-lane DPP sum of one DPP row in every shape.
+// HS: the strided history (BondArgs::hnext; B_hist is not null). A template
+// parameter, so that the dense-history and history-less scans keep their code.
 template <int VARIANT, int R, bool VEC, int P, bool VECI, bool NT = false, int BS = 256, int CB = 64,
-          int DPL = DP_TV, bool RQ = false, typename WT = float>
+          int DPL = DP_TV, bool RQ = false, typename WT = float, bool HS = false>
 __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
   constexpr int LPR = CB / 4, G = BS / LPR;
   static_assert(CB % 64 == 0 && BS % LPR == 0, "a 16-lane DPP row must cover one 64-miner tile");
@@ -4142,6 +4178,9 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
       }
     }
   };
+  // HS: the history countdown, scalars of the block
+  int hnext = HS ? A.hnext : 0;
+  long long hsl = HS ? (long long)A.hslot * N + n : 0;
 #pragma unroll
   for (int k = 0; k < P; ++k)
     if (A.t0 + k < A.t1) fetch(k, A.t0 + k);
@@ -4152,6 +4191,9 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
       const int t = tb + k;
       if (t >= A.t1) break;
       const long long slice = (long long)t * N + n;
+      // store this epoch's state? Block-uniform, from t alone (never a lane's
+      // branch: see the dividend sum below for what those cost here)
+      const bool hst = HS && t == hnext;
       if (!COLNORM && has_old && reset_mode != YUMA_RESET_NONE && t == reset_epoch &&
           (reset_all || (reset_index >= 0 && reset_index < M))) {
         bool fire = reset_mode == YUMA_RESET_ALWAYS;
@@ -4282,8 +4324,8 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
             B[i][c] = mn(nb, 1.0f);
           }
         }
-        if (A.B_hist != nullptr && row < V) {
-          float* hp = A.B_hist + slice * VM + (long long)row * M;
+        if ((HS ? hst : A.B_hist != nullptr) && row < V) {
+          float* hp = A.B_hist + (HS ? hsl : slice) * VM + (long long)row * M;
           if (NT && VEC) {  // write-once history: non-temporal stores
             if (m < M)
               __builtin_nontemporal_store(fvec4{B[i][0], B[i][1], B[i][2], B[i][3]},
@@ -4335,6 +4377,10 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
         } else if ((lane & 15) == 0 && row < V && tile < A.tiles) {
           A.dpart[dp_index(slice, tile, row, A.tiles, V)] = d;
         }
+      }
+      if (HS && hst) {
+        hnext += A.hstride;
+        hsl += N;
       }
       has_old = true;
       if (YUMA2) have_wp = true;
@@ -4390,7 +4436,9 @@ constexpr int kGrpDB = 32;  // epochs of dividend partials parked per wave in LD
 // 2^-25 of it, below the half-ulp of 1 above 1), so the clamp(max = 1) is the
 // identity too and B stays in [0, 1]: the update drops both clamps with the
 // same bits (yumas.py:574-586). NaN operands propagate alike in both forms.
-template <int VARIANT, int K, int R, int P, int LQ, bool HIST, bool BND = false>
+// HS (with HIST): the strided history (BondArgs::hnext), a template parameter
+// so that the dense-history and history-less scans keep their code.
+template <int VARIANT, int K, int R, int P, int LQ, bool HIST, bool BND = false, bool HS = false>
 __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask, float* dpark) {
   constexpr bool LIQ = LQ != 0;
   constexpr int G = 16;
@@ -4511,11 +4559,13 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const long long s0 = (long long)A.t0 * N + min(n0 + k, N - 1);
+    const long long h0 = HS ? (long long)A.hslot * N + min(n0 + k, N - 1) : s0;  // the next slot to write
     fI[k] = A.I + s0 * M + mc;
     fB[k] = A.ba + s0 * M + mc;
     pD[k] = A.dpart + (s0 * A.tiles + tile) * V + row0;
-    pH[k] = hist ? A.B_hist + s0 * VM + (long long)row0 * M + m : nullptr;
+    pH[k] = hist ? A.B_hist + h0 * VM + (long long)row0 * M + m : nullptr;
   }
+  int hnext = HS ? A.hnext : 0;  // HS: the history countdown, a scalar of the block
   auto fetch_s = [&](int k, bool more) {  // as fetch: unconditional, clamped
     const float4 x = *reinterpret_cast<const float4*>(fI[k]);
     ri[k][0] = x.x;
@@ -4589,6 +4639,7 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
     for (int kk = 0; kk < P; ++kk) {
       const int t = tb + kk;
       if (t >= A.t1) break;
+      const bool hst = !HS || t == hnext;  // store this epoch's state (block-uniform, from t alone)
       // normalised weights, once for the K scenarios: div_fast_nz's result
       // from the stored reciprocal when every row of the wave is in range,
       // else IEEE division (the same values up to the sign of a zero)
@@ -4674,7 +4725,7 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
               B[k][i][c] = vmin(nb, 1.0f);
             }
           }
-          if (hist && row < V && m < M)
+          if (hist && hst && row < V && m < M)
             *reinterpret_cast<float4*>(pH[k] + (long long)G * i * M) =
                 make_float4(B[k][i][0], B[k][i][1], B[k][i][2], B[k][i][3]);
           // (a select, not a lane branch: the branch made the compiler wait
@@ -4688,8 +4739,9 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
         }
         fetch_s(k, t + 2 < A.t1);
         pD[k] += sD;
-        if (hist) pH[k] += sM * V;
+        if (hist) pH[k] += hst ? sM * V : 0;  // the walk follows the slots: only a stored epoch moves it
       }
+      if (HS && hst) hnext += A.hstride;
       // the W ring refill after this epoch's per-scenario incentive loads:
       // vmcnt drains in issue order, so waiting for the next epoch's
       // incentive does not wait for the rows two epochs ahead (c3 bonds
@@ -4710,8 +4762,9 @@ __device__ __forceinline__ void grp_scan(const BondArgs& A, unsigned liquid_mask
   }
 }
 
-template <int VARIANT, int K, int R, int P, bool HIST>
+template <int VARIANT, int K, int R, int P, bool HIST, bool HS = false>
 __global__ __launch_bounds__(256, kGrpWaves) void k_bonds_grp(BondArgs A) {
+  static_assert(HIST || !HS, "the strided history is a history");
   __shared__ float dpark[4 * kGrpDB * K * R * 4];
   const int n0 = (blockIdx.x / (A.tiles * A.rowblocks)) * K;
   unsigned liquid_mask = 0;
@@ -4761,20 +4814,20 @@ __global__ __launch_bounds__(256, kGrpWaves) void k_bonds_grp(BondArgs A) {
     }
     if (__all(ok)) {
       if (liquid_mask == (1u << nk) - 1u)
-        grp_scan<VARIANT, K, R, P, 2, HIST, true>(A, liquid_mask, dpark);
+        grp_scan<VARIANT, K, R, P, 2, HIST, true, HS>(A, liquid_mask, dpark);
       else if (liquid_mask != 0)
-        grp_scan<VARIANT, K, R, P, 1, HIST, true>(A, liquid_mask, dpark);
+        grp_scan<VARIANT, K, R, P, 1, HIST, true, HS>(A, liquid_mask, dpark);
       else
-        grp_scan<VARIANT, K, R, P, 0, HIST, true>(A, 0u, dpark);
+        grp_scan<VARIANT, K, R, P, 0, HIST, true, HS>(A, 0u, dpark);
       return;
     }
   }
   if (VARIANT == YUMA_VARIANT_YUMA4 && liquid_mask == (1u << nk) - 1u)  // block-uniform; Yuma3 has no bond_alpha
-    grp_scan<VARIANT, K, R, P, 2, HIST>(A, liquid_mask, dpark);
+    grp_scan<VARIANT, K, R, P, 2, HIST, false, HS>(A, liquid_mask, dpark);
   else if (VARIANT == YUMA_VARIANT_YUMA4 && liquid_mask != 0)
-    grp_scan<VARIANT, K, R, P, 1, HIST>(A, liquid_mask, dpark);
+    grp_scan<VARIANT, K, R, P, 1, HIST, false, HS>(A, liquid_mask, dpark);
   else
-    grp_scan<VARIANT, K, R, P, 0, HIST>(A, 0u, dpark);
+    grp_scan<VARIANT, K, R, P, 0, HIST, false, HS>(A, 0u, dpark);
 }
 
 // ---------------------------------------------------------------------------
@@ -5416,7 +5469,9 @@ int launch_cn(hipStream_t st, yk::BondArgs& A, int* ptiles) {
   constexpr int P = R <= 2 ? 4 : (R == 4 ? 2 : 1);  // epochs in flight
   // RQ: k_rowsum's screened reciprocals (run_impl; not the shard stages)
   with_bool(A.rq4 != nullptr, [&](auto RQ) {
-    YK_LAUNCH((yk::k_bonds_cn<VARIANT, R, P, 8, decltype(RQ)::value>), nblocks, 512, st, A);
+    with_bool(A.B_hist != nullptr && yk::hist_strided(A), [&](auto HS) {
+      YK_LAUNCH((yk::k_bonds_cn<VARIANT, R, P, 8, decltype(RQ)::value, decltype(HS)::value>), nblocks, 512, st, A);
+    });
   });
   return yk::DP_TV;
 }
@@ -5438,9 +5493,19 @@ int launch_bonds_colnorm(RowCfg rc, hipStream_t st, yk::BondArgs& A, int* ptiles
       A.rowblocks = (A.V + yk::kRustBigRows - 1) / yk::kRustBigRows;
       A.cblocks = A.tiles;
       const long long nb = (long long)A.N * A.rowblocks * A.tiles;
+      // one launch pair per epoch: the history countdown (BondArgs::hnext) runs here
+      yk::BondArgs At = A;
+      int hnext = A.hnext, hslot = A.hslot;
       for (int t = A.t0; t < A.t1; ++t) {
-        YK_LAUNCH((yk::k_rust_big_ema<VEC>), nb, 256, st, A, t, A.cpart);
-        YK_LAUNCH((yk::k_rust_big_norm<VEC>), nb, 256, st, A, t, A.cpart);
+        const bool hst = A.B_hist != nullptr && t == hnext;
+        At.B_hist = hst ? A.B_hist : nullptr;
+        At.hslot = hslot;
+        YK_LAUNCH((yk::k_rust_big_ema<VEC>), nb, 256, st, At, t, A.cpart);
+        YK_LAUNCH((yk::k_rust_big_norm<VEC>), nb, 256, st, At, t, A.cpart);
+        if (hst) {
+          hnext += A.hstride;
+          ++hslot;
+        }
       }
       return yk::DP_TV;
     } else {
@@ -5462,20 +5527,23 @@ int launch_bonds_colnorm(RowCfg rc, hipStream_t st, yk::BondArgs& A, int* ptiles
   A.cblocks = A.tiles;
   const long long nblocks = (long long)A.N * A.tiles;
   auto go = [&](auto kern, int nt) { YK_LAUNCH(kern, nblocks, nt, st, A); };
-  switch (rc) {
-    case RC_256_1:
-      go(yk::k_bonds<VARIANT, 256, 1, VEC>, 256);
-      break;
-    case RC_256_4:
-      go(yk::k_bonds<VARIANT, 256, 4, VEC>, 256);
-      break;
-    case RC_256_16:
-      go(yk::k_bonds<VARIANT, 256, 16, VEC>, 256);
-      break;
-    case RC_1024_16:
-      go(yk::k_bonds<VARIANT, 1024, 16, VEC>, 1024);
-      break;
-  }
+  with_bool(A.B_hist != nullptr && yk::hist_strided(A), [&](auto HS) {
+    constexpr bool kHs = decltype(HS)::value;
+    switch (rc) {
+      case RC_256_1:
+        go(yk::k_bonds<VARIANT, 256, 1, VEC, kHs>, 256);
+        break;
+      case RC_256_4:
+        go(yk::k_bonds<VARIANT, 256, 4, VEC, kHs>, 256);
+        break;
+      case RC_256_16:
+        go(yk::k_bonds<VARIANT, 256, 16, VEC, kHs>, 256);
+        break;
+      case RC_1024_16:
+        go(yk::k_bonds<VARIANT, 1024, 16, VEC, kHs>, 1024);
+        break;
+    }
+  });
   return yk::DP_TV;
 }
 
@@ -5507,26 +5575,32 @@ constexpr int kScanGroup = 4;  // scenarios per block of the shared-input scan
 constexpr bool kElemRq(int variant, bool hist) { return hist ? variant <= YUMA_VARIANT_YUMA2 : true; }
 int bonds_rows(bool vec, bool hist, bool wsh) { return vec && (hist || wsh) ? 2 : 1; }
 template <typename WT, int VARIANT, int R, bool VEC, int P, bool VECI, bool NT, int BS, int CB, int DPL,
-          bool RQ = false>
+          bool RQ = false, bool HS = false>
 int launch_elem_shape(hipStream_t st, yk::BondArgs& A) {
   constexpr int G = BS / (CB / 4);
   A.rowblocks = (A.V + G * R - 1) / (G * R);
   A.cblocks = (A.M + CB - 1) / CB;
   const long long nblocks = (long long)A.N * A.rowblocks * A.cblocks;
-  YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT>), nblocks, BS, st, A);
+  YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS>), nblocks, BS, st, A);
   return DPL;
 }
 // WT: the element type A.W addresses (uint16 weights: Yuma 3 / Yuma 4, never
 // the shared-input sweep scan)
+// A strided history (hist_strided) runs the dense history's shape at every
+// stride, in that shape's HS instantiation ("Strided bond history").
 template <int VARIANT, bool VEC, typename WT>
 int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
   const bool hist = A.B_hist != nullptr;
+  const bool hs = hist && yk::hist_strided(A);
   if constexpr (VEC) {
     if (hist && A.M >= 1024) {
       constexpr int P = VARIANT <= YUMA_VARIANT_YUMA2 ? kWidePCn : kWideP;
       return with_bool(kElemRq(VARIANT, true) && A.rq4 != nullptr, [&](auto RQ) {
         constexpr bool kRq = kElemRq(VARIANT, true) && decltype(RQ)::value;
-        return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, kRq>(st, A);
+        return with_bool(hs, [&](auto HS) {
+          return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, kRq,
+                                   decltype(HS)::value>(st, A);
+        });
       });
     }
   }
@@ -5536,9 +5610,12 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
       A.rowblocks = (A.V + 16 * R - 1) / (16 * R);
       A.cblocks = A.tiles;
       const long long nblocks = (long long)((A.N + K - 1) / K) * A.rowblocks * A.tiles;
-      with_bool(hist, [&](auto HIST) {
-        YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, decltype(HIST)::value>), nblocks, 256, st, A);
-      });
+      if (hs)
+        YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, true, true>), nblocks, 256, st, A);
+      else
+        with_bool(hist, [&](auto HIST) {
+          YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, decltype(HIST)::value>), nblocks, 256, st, A);
+        });
       return yk::DP_TV;
     }
   }
@@ -5548,6 +5625,13 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
     // c2's 512 such blocks 0.99 -> 1.31, so one row per lane there
     const long long blocks_r2 = (long long)A.N * ((A.V + 7) / 8) * ((A.M + 255) / 256);
     constexpr bool kRqOk = VEC && kElemRq(VARIANT, false);
+    if constexpr (!VEC) {  // the scalar form writes its history from these shapes
+      if (hs) {
+        if (blocks_r2 >= 4096)
+          return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, false, true>(st, A);
+        return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, false, true>(st, A);
+      }
+    }
     return with_bool(kRqOk && A.rq4 != nullptr, [&](auto RQ) {
       constexpr bool kRq = kRqOk && decltype(RQ)::value;
       if (blocks_r2 >= 4096)
@@ -5555,6 +5639,7 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
       return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, kRq>(st, A);
     });
   }
+  if (hs) return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, true, 256, 64, yk::DP_TV, false, true>(st, A);
   return with_bool(hist, [&](auto HIST) {  // the history goes out with non-temporal stores
     return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, decltype(HIST)::value, 256, 64, yk::DP_TV>(st, A);
   });
@@ -5690,8 +5775,15 @@ yk::BondArgs bond_args(const float* W, const Workspace& ws, const Bufs& b, const
   A.t0 = 0;
   A.t1 = E;
   A.ep = dte_stride(E);
+  A.hstride = 1;  // the dense history: slot == epoch (run_impl sets a stride's countdown)
+  A.hnext = 0;
+  A.hslot = 0;
   return A;
 }
+
+// Slots of a history of stride s >= 1 from first epoch f >= 0 over E epochs
+// (yuma_hist_slots): the stored epochs are f + j s < E.
+long long hist_slots(int E, int s, int f) { return f < E ? ((long long)E - 1 - f) / s + 1 : 0; }
 
 // D / Dn (and T_v) of ns slices from the dividend partials in layout dpl
 void launch_finalize(hipStream_t st, long long ns, const float* dsrc, const Workspace& ws, int variant, int V,
@@ -5711,7 +5803,7 @@ template <typename WT>
 int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, const WT* W,
              const float* S, const float* B_init, const float* Wprev_init,
              const yuma_outputs_t* out, void* workspace, size_t ws_bytes, int chunk,
-             void* stream, float* phase_ms = nullptr, int wsh = 0) {
+             void* stream, float* phase_ms = nullptr, int wsh = 0, int hist_stride = 1, int hist_first = 0) {
   constexpr bool U16 = std::is_same_v<WT, uint16_t>;
   static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
   if (const int err = check_sizes(variant, N, E, V, M)) return err;
@@ -5848,6 +5940,15 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
     A.t0 = c0;
     A.t1 = c1;
     A.wsh = wsh;
+    {
+      // the history countdown of this chunk (BondArgs::hnext): epochs count
+      // from the run's epoch 0, so the slot follows the absolute epoch
+      const long long j = c0 <= hist_first ? 0 : ((long long)c0 - hist_first + hist_stride - 1) / hist_stride;
+      const long long next = hist_first + j * hist_stride;
+      A.hstride = hist_stride < E ? hist_stride : E;
+      A.hnext = next < E ? (int)next : -1;
+      A.hslot = next < E ? (int)j : 0;
+    }
     tm.mark(YUMA_PHASE_BONDS);
     int ptiles = tiles;
     int dpl;
@@ -6010,6 +6111,25 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
 
 constexpr int kRunFlags = YUMA_RUN_SHARED_INPUTS | YUMA_RUN_W_U16;
 
+namespace {
+// yuma_run_options_t checked and resolved: NULL is every default; stride 0 is 1.
+struct RunOpts {
+  int flags, stride, first;
+};
+int read_opts(const yuma_run_options_t* o, RunOpts* r) {
+  *r = RunOpts{0, 1, 0};
+  if (o == nullptr) return YUMA_OK;
+  if (o->flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", o->flags);
+  if (o->hist_stride < 0 || o->hist_first < 0)
+    return fail(YUMA_EINVAL, "hist_stride=%d and hist_first=%d must not be negative", o->hist_stride,
+                o->hist_first);
+  for (int w : o->reserved)
+    if (w != 0) return fail(YUMA_EINVAL, "yuma_run_options_t.reserved must be 0");
+  *r = RunOpts{o->flags, o->hist_stride == 0 ? 1 : o->hist_stride, o->hist_first};
+  return YUMA_OK;
+}
+}  // namespace
+
 struct yuma_graph {
   hipGraph_t graph;
   hipGraphExec_t exec;
@@ -6041,6 +6161,28 @@ int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int 
                     Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh);
   return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
                   workspace_bytes, chunk_epochs, stream, phase_ms, wsh);
+}
+
+int yuma_run_opts(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
+                  const float* W, const float* S, const float* B_init, const float* Wprev_init,
+                  const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
+                  int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms) {
+  RunOpts o;
+  if (const int err = read_opts(opts, &o)) return err;
+  const int wsh = (o.flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
+  if (o.flags & YUMA_RUN_W_U16)
+    return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
+                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride,
+                    o.first);
+  return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride, o.first);
+}
+
+int yuma_hist_slots(int E, int hist_stride, int hist_first) {
+  if (E < 1 || hist_stride < 0 || hist_first < 0)
+    return fail(YUMA_EINVAL, "yuma_hist_slots: E=%d must be positive, hist_stride=%d and hist_first=%d not negative",
+                E, hist_stride, hist_first);
+  return (int)hist_slots(E, hist_stride == 0 ? 1 : hist_stride, hist_first);
 }
 
 int yuma_u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
@@ -6086,11 +6228,14 @@ int yuma_shard_stage(int stage, int variant, const yuma_params_t* params_dev, in
                           out, workspace, workspace_bytes, stream);
 }
 
-int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
-                         int E, int V, int M, const float* W, const float* S,
-                         const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
-                         void* workspace, size_t workspace_bytes, int chunk_epochs, int flags) {
-  if (flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
+int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                           int E, int V, int M, const float* W, const float* S,
+                           const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                           void* workspace, size_t workspace_bytes, int chunk_epochs,
+                           const yuma_run_options_t* opts) {
+  RunOpts o;
+  if (const int err = read_opts(opts, &o)) return err;
+  const int flags = o.flags;
   if (graph == nullptr) return fail(YUMA_EINVAL, "graph handle pointer is NULL");
   *graph = nullptr;
   const int wsh = (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
@@ -6107,9 +6252,9 @@ int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* 
   const int rc = (flags & YUMA_RUN_W_U16)
                      ? run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S,
                                 B_init, Wprev_init, out, workspace, workspace_bytes, chunk_epochs, cs,
-                                nullptr, wsh)
+                                nullptr, wsh, o.stride, o.first)
                      : run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                                workspace_bytes, chunk_epochs, cs, nullptr, wsh);
+                                workspace_bytes, chunk_epochs, cs, nullptr, wsh, o.stride, o.first);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(cs, &g);
   (void)hipStreamDestroy(cs);
@@ -6126,6 +6271,17 @@ int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* 
   }
   *graph = new yuma_graph{g, x};
   return YUMA_OK;
+}
+
+int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                         int E, int V, int M, const float* W, const float* S,
+                         const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                         void* workspace, size_t workspace_bytes, int chunk_epochs, int flags) {
+  if (flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
+  yuma_run_options_t o{};
+  o.flags = flags;
+  return yuma_graph_create_opts(graph, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out,
+                                workspace, workspace_bytes, chunk_epochs, &o);
 }
 
 int yuma_graph_create(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,

@@ -44,11 +44,14 @@ EXPORTED_SYMBOLS = (
     "yuma_run",
     "yuma_run_profiled",
     "yuma_run_ex",
+    "yuma_run_opts",
+    "yuma_hist_slots",
     "yuma_epoch",
     "yuma_synth_weights",
     "yuma_shard_stage",
     "yuma_graph_create",
     "yuma_graph_create_ex",
+    "yuma_graph_create_opts",
     "yuma_graph_launch",
     "yuma_graph_nodes",
     "yuma_graph_destroy",
@@ -128,6 +131,15 @@ SHARD_IO_FIELDS = ("rowsum_part", "rowsum", "csum_part", "csum_part_d", "csum", 
                    "levels", "rsum_part", "rsum", "levels_all", "dsum_part", "dsum", "tv_part", "tv")
 
 
+class YumaRunOptionsC(ctypes.Structure):
+    """yuma_run_options_t (include/yuma_hip.h): 32 bytes."""
+    _fields_ = [("flags", ctypes.c_int32), ("hist_stride", ctypes.c_int32), ("hist_first", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+assert ctypes.sizeof(YumaRunOptionsC) == 32, ctypes.sizeof(YumaRunOptionsC)
+
+
 class YumaShardIOC(ctypes.Structure):
     """yuma_shard_io_t (include/yuma_hip.h): two ints, then device pointers."""
     _fields_ = [("M_total", ctypes.c_int), ("col0", ctypes.c_int)] + [
@@ -162,6 +174,10 @@ def load_library(path: str | None = None):
         lib.yuma_run_profiled.restype = i32
         lib.yuma_run_ex.argtypes = lib.yuma_run.argtypes[:-1] + [i32, vp, ctypes.POINTER(ctypes.c_float)]
         lib.yuma_run_ex.restype = i32
+        lib.yuma_run_opts.argtypes = lib.yuma_run.argtypes[:-1] + [vp, vp, ctypes.POINTER(ctypes.c_float)]
+        lib.yuma_run_opts.restype = i32
+        lib.yuma_hist_slots.argtypes = [i32, i32, i32]
+        lib.yuma_hist_slots.restype = i32
         # (not in EXPORTED_SYMBOLS: that tuple mirrors the header scan of
         # test_host.py, whose pattern takes lower-case letters only)
         lib.yuma_u16_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
@@ -178,6 +194,8 @@ def load_library(path: str | None = None):
         lib.yuma_graph_create.restype = i32
         lib.yuma_graph_create_ex.argtypes = lib.yuma_graph_create.argtypes + [i32]
         lib.yuma_graph_create_ex.restype = i32
+        lib.yuma_graph_create_opts.argtypes = lib.yuma_graph_create.argtypes + [vp]
+        lib.yuma_graph_create_opts.restype = i32
         lib.yuma_graph_launch.argtypes = [vp, vp]
         lib.yuma_graph_launch.restype = i32
         lib.yuma_graph_nodes.argtypes = [vp]
@@ -438,8 +456,9 @@ class RunResult:
     C: torch.Tensor                   # [E, N, M]
     I: torch.Tensor                   # [E, N, M]
     B_final: torch.Tensor             # [N, V, M]
-    B_hist: torch.Tensor | None       # [E, N, V, M]
+    B_hist: torch.Tensor | None       # [E, N, V, M]; [len(hist_epochs), N, V, M] under a history stride
     extra: dict
+    hist_epochs: tuple[int, ...] | None = None  # the epoch each B_hist slice holds (None: no history)
 
 
 def _as_dev(x: torch.Tensor, dev) -> torch.Tensor:
@@ -485,6 +504,27 @@ def to_u16(W: torch.Tensor) -> torch.Tensor:
     return torch.from_numpy(np.rint(q.numpy()).astype(np.uint16))  # rint: half to even
 
 
+def hist_epochs(E: int, stride: int = 1, first: int | None = None) -> tuple[int, ...]:
+    """The epochs whose bond state a run of E epochs stores under a history
+    stride: first, first + stride, ... below E. first=None is stride - 1, the
+    state after every stride-th epoch. Host only (needs the library, not a
+    GPU): the count is cross-checked against yuma_hist_slots."""
+    E, stride = operator.index(E), operator.index(stride)
+    if E < 1:
+        raise ValueError(f"E={E} must be positive")
+    if stride < 1:
+        raise ValueError(f"hist_stride={stride} must be at least 1")
+    first = stride - 1 if first is None else operator.index(first)
+    if first < 0:
+        raise ValueError(f"hist_first={first} must not be negative")
+    epochs = tuple(range(first, E, stride))
+    if max(E, stride, first) < 2**31:  # (beyond int32 the C entry point cannot be asked)
+        n = int(load_library().yuma_hist_slots(E, stride, first))
+        if n != len(epochs):
+            raise EngineError(f"yuma_hist_slots({E}, {stride}, {first}) = {n}, expected {len(epochs)}")
+    return epochs
+
+
 def workspace_bytes(variant: int, N: int, E: int, V: int, M: int, full: bool) -> int:
     return int(load_library().yuma_workspace_bytes(variant, N, E, V, M, 1 if full else 0))
 
@@ -494,7 +534,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         want_hist: bool = False, want: tuple[str, ...] = (), chunk_epochs: int = 0,
         workspace: torch.Tensor | None = None, out: dict | None = None,
         phase_ms: list | None = None, capture: list | None = None,
-        single_call: bool = False, shared_inputs: bool = False) -> RunResult:
+        single_call: bool = False, shared_inputs: bool = False,
+        hist_stride: int = 1, hist_first: int | None = None) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -502,7 +543,12 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     shared_inputs: W [E,1,V,M] and S [E,1,V] are one trajectory that every
     scenario (one per params record) reads — a parameter sweep over one subnet
     (yuma_run_ex, YUMA_RUN_SHARED_INPUTS); results equal a run on W and S
-    replicated per scenario."""
+    replicated per scenario.
+    hist_stride, hist_first: with want_hist (or out["B_hist"]), store the bond
+    state after the epochs hist_epochs(E, hist_stride, hist_first) only:
+    B_hist is [n_hist, N, V, M], slice j bit-equal to the dense history's slice
+    at RunResult.hist_epochs[j] (yuma_run_opts). hist_first=None is
+    hist_stride - 1. Stride 1 from epoch 0 is the dense history."""
     E, Nw, V, M = W.shape
     check_limits(V, M)
     dev = device()
@@ -510,6 +556,10 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     if S.shape != (E, Nw, V):
         raise ValueError(f"S shape {tuple(S.shape)} does not match W {tuple(W.shape)}")
     n_scen = len(params) if shared_inputs else Nw
+    h_epochs = hist_epochs(E, hist_stride, hist_first)
+    strided = len(h_epochs) != E  # stride 1 from epoch 0 stores all E epochs: the dense history
+    if strided and single_call:
+        raise ValueError("single_call (yuma_epoch) keeps the dense history: no hist_stride / hist_first")
     for name, t in (("B_init", B_init), ("Wprev_init", Wprev_init)):
         # the kernels index it n * V * M + row * M + m: a smaller tensor is read past its end
         if t is not None and tuple(t.shape) != (n_scen, V, M):
@@ -549,7 +599,12 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     need("I", (E, N, M))
     need("B_final", (N, V, M))
     if want_hist:
-        need("B_hist", (E, N, V, M))
+        need("B_hist", (len(h_epochs), N, V, M))
+    if o.get("B_hist") is not None:
+        # the kernels index it slot * N * V * M + ...: a smaller tensor is written past its end
+        if tuple(o["B_hist"].shape) != (len(h_epochs), N, V, M):
+            raise ValueError(f"out['B_hist'] shape {tuple(o['B_hist'].shape)} is not "
+                             f"[n_hist={len(h_epochs)}, N={N}, V={V}, M={M}]")
     shapes = {
         "D": (E, N, V), "R": (E, N, M), "P": (E, N, M), "T": (E, N, M), "Tv": (E, N, V),
         "Sn": (E, N, V), "bond_alpha": (E, N, M), "alpha_ab": (E, N, 2),
@@ -576,7 +631,22 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
             w_u16 = False
             W = _as_dev(W, dev)
             args = args[:6] + (W.data_ptr(),) + args[7:]
-    if w_u16:  # yuma_run_ex / yuma_graph_create_ex with YUMA_RUN_W_U16
+    if strided:  # yuma_run_opts / yuma_graph_create_opts: the history stride, with the run's flags
+        opts = YumaRunOptionsC(flags=(RUN_W_U16 if w_u16 else 0) | (RUN_SHARED_INPUTS if shared_inputs else 0),
+                               # (a stride of E or more stores one epoch at the most: int32 either way)
+                               hist_stride=min(int(hist_stride), E), hist_first=h_epochs[0] if h_epochs else E)
+        if capture is not None:
+            h = ctypes.c_void_p()
+            torch.cuda.synchronize(dev)
+            _check(lib.yuma_graph_create_opts(ctypes.byref(h), *args[:-1], ctypes.addressof(opts)),
+                   "yuma_graph_create_opts")
+            capture.append(h)
+        else:
+            buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
+            _check(lib.yuma_run_opts(*args[:-1], ctypes.addressof(opts), stream, buf), "yuma_run_opts")
+            if phase_ms is not None:
+                phase_ms[:] = list(buf)
+    elif w_u16:  # yuma_run_ex / yuma_graph_create_ex with YUMA_RUN_W_U16
         if capture is not None:
             h = ctypes.c_void_p()
             torch.cuda.synchronize(dev)
@@ -617,7 +687,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
     keep["w_path"] = "u16" if w_u16 else "f32"  # how W was read: natively as uint16, or as fp32
-    return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], o.get("B_hist"), keep)
+    hist = o.get("B_hist")
+    return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs)
 
 
 class RunGraph:

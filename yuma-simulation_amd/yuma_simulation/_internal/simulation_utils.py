@@ -16,6 +16,7 @@ Drop-in for the reference's _internal/simulation_utils.py:
 from __future__ import annotations
 
 import gc
+import operator
 from contextlib import contextmanager
 
 from collections import defaultdict
@@ -91,15 +92,21 @@ def _reward_key(config: YumaConfig) -> tuple:
 
 
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
-                    want_incentives: bool = True):
+                    want_incentives: bool = True, bonds_every: int = 1):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
-    tuple per run, in order."""
+    tuple per run, in order.
+    bonds_every: each run's bonds list holds the bond states after the epochs
+    engine.hist_epochs(E, bonds_every) only (every bonds_every-th epoch), in
+    order; the engine stores no other (engine.run's hist_stride). Dividends
+    and incentives stay per epoch."""
+    if operator.index(bonds_every) < 1:
+        raise ValueError(f"bonds_every={bonds_every} must be at least 1")
     # the result lists are thousands of fresh containers (the sheet: 1512
     # dividend lists): the cyclic collector would sweep the process's whole
     # heap several times while they are built; they hold no cycles
     with _no_cyclic_gc():
-        return _run_simulations(runs, want_bonds, want_incentives)
+        return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every))
 
 
 @contextmanager
@@ -156,7 +163,7 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
-                     totals: bool = False):
+                     totals: bool = False, bonds_every: int = 1):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -196,7 +203,8 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
                     local[lk] = rec
             params.append(rec)
         W, S, S_host = _group_inputs([packed[k] for k in idx], E * V * M * len(idx))
-        launched.append((E, V, idx, S_host, engine.run(variant, params, W, S, want_hist=want_bonds)))
+        launched.append((E, V, idx, S_host, engine.run(variant, params, W, S, want_hist=want_bonds,
+                                                              hist_stride=bonds_every)))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
         hist = res.B_hist.cpu() if want_bonds else None
@@ -228,7 +236,7 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
                 div = {validator: cols[i] for i, validator in enumerate(r.case.validators)}
             else:
                 div = _dividends_per_1000_tao(r.case, r.yuma_config, packed[k][3].cpu(), Dn[:, j])
-            bonds = [hist[e, j].clone().to(home) for e in range(E)] if want_bonds else []
+            bonds = [hist[e, j].clone().to(home) for e in range(hist.shape[0])] if want_bonds else []
             incentives = [inc[e, j].clone().to(home) for e in range(E)] if want_incentives else []
             results[k] = (div, bonds, incentives)
     return results
