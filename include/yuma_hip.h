@@ -121,7 +121,8 @@ typedef struct yuma_outputs {
   float* Wb;         /* [E][N][V][M] weight_for_bond (Yuma1/Yuma2)               */
   float* B_inst;     /* [E][N][V][M] validator_bond (Rust/Yuma1/Yuma2)           */
   float* B_hist;     /* [E][N][V][M] bond state after each epoch (bonds_per_epoch);
-                        [n_hist][N][V][M] under a history stride (yuma_run_opts)   */
+                        [n_hist][N][V][M] under a history stride (yuma_run_opts);
+                        bfloat16 elements under YUMA_RUN_HIST_BF16                 */
   float* B_final;    /* [N][V][M]    bond state after the last epoch             */
 } yuma_outputs_t;
 
@@ -174,8 +175,25 @@ int yuma_run(int variant, const yuma_params_t* params_dev, int N, int E, int V, 
  * aligned). Accepted by yuma_run_ex and yuma_graph_create_ex where
  * yuma_u16_native() returns 1; elsewhere they return YUMA_EUNSUPPORTED before
  * the first launch and the caller widens W itself. Every other entry point
- * reads fp32 weights only.                                                   */
-enum yuma_run_flags { YUMA_RUN_SHARED_INPUTS = 1, YUMA_RUN_W_U16 = 2 };
+ * reads fp32 weights only.
+ * YUMA_RUN_HIST_BF16 — out->B_hist addresses bfloat16 elements (2 bytes: the
+ * upper half of an fp32) in the same [E or n_hist][N][V][M] layout, written
+ * by the bond scan itself: element = RNE(fp32 bond state) for every finite
+ * value (a value above the largest finite bfloat16 rounds to infinity, as RNE
+ * has it); a NaN stays a NaN, payload unspecified. bfloat16 keeps fp32's
+ * exponent range, which Yuma 3's bonds (scaled by maxint = 2^64) need. The
+ * history is never fed back into the recurrence: Dn, C, I, B_final and every
+ * other output have the bits of the fp32-history run, for half the history's
+ * memory and write traffic. A bfloat16 history is for reading, not for
+ * resuming: resume from B_final (fp32). B_hist must be non-NULL
+ * (YUMA_EINVAL) and 8-byte aligned. Accepted by yuma_run_ex, yuma_run_opts,
+ * yuma_graph_create_ex and yuma_graph_create_opts where
+ * yuma_hist_bf16_native() returns 1; elsewhere they return YUMA_EUNSUPPORTED
+ * before the first launch and the caller converts an fp32 history itself.
+ * Combines with YUMA_RUN_W_U16 and with the history stride. yuma_epoch,
+ * yuma_run, yuma_run_profiled, yuma_graph_create and yuma_shard_stage write an
+ * fp32 history only.                                                         */
+enum yuma_run_flags { YUMA_RUN_SHARED_INPUTS = 1, YUMA_RUN_W_U16 = 2, YUMA_RUN_HIST_BF16 = 4 };
 int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                 const float* W, const float* S, const float* B_init, const float* Wprev_init,
                 const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
@@ -195,8 +213,8 @@ int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int 
  * stores, the others skip the store on a block-uniform test of the epoch. On
  * MI355X at 256 x 4096, 1000 epochs, the dense history is 4.19 GB of the bond
  * scan's 8.5 GB of traffic (measured effect: README.md, profiles/hist_stride/).
- * Combines with YUMA_RUN_SHARED_INPUTS and YUMA_RUN_W_U16 as the dense
- * history does. opts NULL: every default. hist_stride < 0, hist_first < 0, an
+ * Combines with YUMA_RUN_SHARED_INPUTS, YUMA_RUN_W_U16 and
+ * YUMA_RUN_HIST_BF16 as the dense history does. opts NULL: every default. hist_stride < 0, hist_first < 0, an
  * unknown flag or a non-zero reserved word return YUMA_EINVAL before the first
  * launch. The workspace size does not depend on the options.
  * yuma_epoch and yuma_shard_stage (the wide-subnet path) keep the dense
@@ -225,6 +243,16 @@ int yuma_hist_slots(int E, int hist_stride, int hist_first);
  * requested.                                                                */
 int yuma_u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out,
                     int flags);
+
+/* 1 when a run with these arguments and YUMA_RUN_HIST_BF16 (`flags`: the
+ * run's other flags) writes its bond history as bfloat16, else 0. Host only,
+ * needs no GPU; of `out` it reads only whether B_hist is non-NULL. Native:
+ * Yuma 3 and Yuma 4 (scalar or liquid alpha, any reset mode), any V up to
+ * YUMA_MAX_VALIDATORS, M % 4 == 0, no YUMA_RUN_SHARED_INPUTS, out->B_hist
+ * requested. (A run also needs the alignment of the vector form: B_hist 8
+ * bytes, W and the fp32 matrices as YUMA_RUN_W_U16 states.)                 */
+int yuma_hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out,
+                          int flags);
 
 /* hipGraph form of yuma_run: the whole multi-epoch run (every phase of every
  * chunk, no host work between them) captured once into a HIP graph and

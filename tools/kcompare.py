@@ -1,0 +1,83 @@
+"""Compare the bond-scan kernels of two builds of the engine library (code-object
+metadata and code bytes; no GPU needed): code size, VGPR / SGPR counts, spills,
+scratch, LDS and kernel-argument size of every k_bonds* / k_rust_big_* kernel
+that both hold, and whether its machine code is byte-identical.
+    python tools/kcompare.py parent/libyuma_hip.so [this/libyuma_hip.so] [-v]
+k_bonds_elem's trailing history element type (HT = float, the default) is
+dropped from a name before the two sides are matched, so that a library built
+before that parameter existed pairs with one built after."""
+import hashlib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+LLVM = "/opt/rocm/lib/llvm/bin"
+FIELDS = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
+          "group_segment_fixed_size", "kernarg_segment_size")
+TAIL = "EEvNS_8BondArgsE"
+
+
+def kernels(lib):
+    """mangled name -> (code bytes, sha1 of the code, the metadata FIELDS)"""
+    with tempfile.TemporaryDirectory() as t:
+        subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={t}/fb", lib], check=True)
+        subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={t}/fb",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={t}/co"], check=True)
+        run = lambda *a: subprocess.run(a, capture_output=True, text=True, check=True).stdout
+        notes = run(f"{LLVM}/llvm-readobj", "--notes", f"{t}/co")
+        m = re.search(r"\.text\s+PROGBITS\s+([0-9a-f]+)\s+([0-9a-f]+)", run(f"{LLVM}/llvm-readelf", "-SW", f"{t}/co"))
+        addr, off = int(m.group(1), 16), int(m.group(2), 16)
+        data = open(f"{t}/co", "rb").read()
+        code = {}
+        for line in run(f"{LLVM}/llvm-readelf", "-sW", f"{t}/co").splitlines():
+            f = line.split()
+            if len(f) >= 8 and f[3] == "FUNC":
+                o, n = off + int(f[1], 16) - addr, int(f[2])
+                code[f[7]] = (n, hashlib.sha1(data[o:o + n]).hexdigest())
+    out = {}
+    for e in re.split(r"\n\s*- \.agpr_count", notes):
+        m = re.search(r"\.name:\s+(\S+)", e)
+        if not m or not re.search(r"k_bonds|k_rust_big", m.group(1)):
+            continue
+        meta = tuple((re.search(r"\." + k + r":\s+(\d+)", e) or [None, "-"])[1] for k in FIELDS)
+        out[m.group(1)] = code.get(m.group(1), (None, None)) + (meta,)
+    return out
+
+
+def key(name):
+    # <..., WT, HS, HT = float> ends in Lb0Ef / Lb1Ef; without HT the name ends in Lb0E / Lb1E
+    if "k_bonds_elemI" in name and re.search(r"Lb[01]Ef" + TAIL + "$", name):
+        return name[:-len("f" + TAIL)] + TAIL
+    return name
+
+
+def main():
+    args = [a for a in sys.argv[1:] if a != "-v"]
+    a = kernels(args[0])
+    b = kernels(args[1] if len(args) > 1 else os.path.join(ROOT, "yuma-simulation_amd", "lib", "libyuma_hip.so"))
+    A = {key(k): v for k, v in a.items()}
+    B = {key(k): v for k, v in b.items()}
+    both = sorted(set(A) & set(B))
+    meta = [k for k in both if (A[k][0], A[k][2]) != (B[k][0], B[k][2])]
+    code = [k for k in both if A[k][1] != B[k][1]]
+    print(f"bond-scan kernels: {len(A)} in the first library, {len(B)} in the second, {len(both)} in both")
+    print(f"  code size / registers / spills / scratch / LDS / kernarg differ: {len(meta)}")
+    print(f"  machine code differs: {len(code)}")
+    print(f"  only in the first: {len(set(A) - set(B))}")
+    for k in sorted(set(meta) | set(code)):
+        print("DIFF", k, A[k], B[k])
+    head = "code " + " ".join(f.replace("_count", "").replace("_fixed_size", "").replace("_segment", "") for f in FIELDS)
+    print(f"only in the second ({len(set(B) - set(A))}): {head}")
+    for k in sorted(set(B) - set(A)):
+        print(" ", k, B[k][0], *B[k][2])
+    if "-v" in sys.argv:
+        print(f"in both: {head}")
+        for k in both:
+            print(" ", k, A[k][0], *A[k][2])
+
+
+if __name__ == "__main__":
+    main()

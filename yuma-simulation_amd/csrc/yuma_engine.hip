@@ -64,6 +64,8 @@ constexpr int kRegRows = YUMA_REG_VALIDATORS;
 typedef float fvec4 __attribute__((ext_vector_type(4)));       // miner columns per tile: 16 lanes x float4
 // uint16 weights (YUMA_RUN_W_U16): a lane's 4 miner columns are one 8-byte load
 typedef unsigned short usvec4 __attribute__((ext_vector_type(4)));
+// bfloat16 bond history (YUMA_RUN_HIST_BF16): a lane's 4 columns are one 8-byte store
+typedef __bf16 bvec4 __attribute__((ext_vector_type(4)));
 constexpr int kMaxTiles = 1 << 20;
 
 // ---------------------------------------------------------------------------
@@ -3243,7 +3245,16 @@ struct BondArgs {
   // hstride and the slot by one; no epoch takes a modulo. The dense history is
   // hstride = 1, hnext = hslot = t0 (hist_strided() is false, slot == epoch).
   int hstride, hnext, hslot;
+  // bfloat16 history (YUMA_RUN_HIST_BF16): B_hist addresses __bf16 elements in
+  // the same [slot][N][V][M] layout. Read on the host only: launch_bonds_elem
+  // picks the HT = __bf16 instantiation of k_bonds_elem from it, no kernel
+  // tests it. The word fills what was the record's tail padding (20 pointers
+  // and 13 ints left 4 bytes), so sizeof(BondArgs), every other field's offset
+  // and with them every existing kernel's argument block and code stay as they
+  // were; slots and the countdown above count elements of either type alike.
+  int hbf16;
 };
+static_assert(sizeof(BondArgs) == 216, "hbf16 sits in the former tail padding: the argument block keeps its size");
 __host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
   return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
 }
@@ -4040,9 +4051,18 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // of each 64-miner tile is the 16-lane DPP sum of one DPP row in every shape.
 // HS: the strided history (BondArgs::hnext; B_hist is not null). A template
 // parameter, so that the dense-history and history-less scans keep their code.
+// HT: the history's element type, float or __bf16 (BondArgs::hbf16). A bf16
+// history stores RNE(B) of the lane's four fp32 bond values (v_cvt_pk_bf16_f32;
+// a NaN stays a NaN) as one 8-byte non-temporal vector; the state, the
+// dividend partials and Bstate are formed from the fp32 registers, so every
+// other output keeps the fp32-history run's bits. Only the two vector shapes
+// that write a history (wide, 64-miner tile) are instantiated for it.
 template <int VARIANT, int R, bool VEC, int P, bool VECI, bool NT = false, int BS = 256, int CB = 64,
-          int DPL = DP_TV, bool RQ = false, typename WT = float, bool HS = false>
+          int DPL = DP_TV, bool RQ = false, typename WT = float, bool HS = false, typename HT = float>
 __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
+  static_assert(std::is_same_v<HT, float> || (std::is_same_v<HT, __bf16> && NT && VEC && !RQ &&
+                                              VARIANT >= YUMA_VARIANT_YUMA3),
+                "bf16 history: Yuma 3 / Yuma 4, vector form, non-temporal stores");
   constexpr int LPR = CB / 4, G = BS / LPR;
   static_assert(CB % 64 == 0 && BS % LPR == 0, "a 16-lane DPP row must cover one 64-miner tile");
   const int cq = threadIdx.x % LPR, lane = threadIdx.x & 63;
@@ -4325,13 +4345,22 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
           }
         }
         if ((HS ? hst : A.B_hist != nullptr) && row < V) {
-          float* hp = A.B_hist + (HS ? hsl : slice) * VM + (long long)row * M;
-          if (NT && VEC) {  // write-once history: non-temporal stores
-            if (m < M)
-              __builtin_nontemporal_store(fvec4{B[i][0], B[i][1], B[i][2], B[i][3]},
-                                          reinterpret_cast<fvec4*>(hp + m));
+          if constexpr (std::is_same_v<HT, float>) {
+            float* hp = A.B_hist + (HS ? hsl : slice) * VM + (long long)row * M;
+            if (NT && VEC) {  // write-once history: non-temporal stores
+              if (m < M)
+                __builtin_nontemporal_store(fvec4{B[i][0], B[i][1], B[i][2], B[i][3]},
+                                            reinterpret_cast<fvec4*>(hp + m));
+            } else {
+              store4<VEC>(hp, m, M, B[i]);
+            }
           } else {
-            store4<VEC>(hp, m, M, B[i]);
+            // M % 4 == 0 and B_hist 8-byte aligned (run_impl): the quad is
+            // wholly inside the row or outside it, and its 8 bytes are aligned
+            __bf16* hp = reinterpret_cast<__bf16*>(A.B_hist) + (HS ? hsl : slice) * VM + (long long)row * M;
+            if (m < M)
+              __builtin_nontemporal_store(__builtin_convertvector(fvec4{B[i][0], B[i][1], B[i][2], B[i][3]}, bvec4),
+                                          reinterpret_cast<bvec4*>(hp + m));
           }
         }
         float d = 0.0f;
@@ -5575,23 +5604,38 @@ constexpr int kScanGroup = 4;  // scenarios per block of the shared-input scan
 constexpr bool kElemRq(int variant, bool hist) { return hist ? variant <= YUMA_VARIANT_YUMA2 : true; }
 int bonds_rows(bool vec, bool hist, bool wsh) { return vec && (hist || wsh) ? 2 : 1; }
 template <typename WT, int VARIANT, int R, bool VEC, int P, bool VECI, bool NT, int BS, int CB, int DPL,
-          bool RQ = false, bool HS = false>
+          bool RQ = false, bool HS = false, typename HT = float>
 int launch_elem_shape(hipStream_t st, yk::BondArgs& A) {
   constexpr int G = BS / (CB / 4);
   A.rowblocks = (A.V + G * R - 1) / (G * R);
   A.cblocks = (A.M + CB - 1) / CB;
   const long long nblocks = (long long)A.N * A.rowblocks * A.cblocks;
-  YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS>), nblocks, BS, st, A);
+  YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS, HT>), nblocks, BS, st, A);
   return DPL;
 }
 // WT: the element type A.W addresses (uint16 weights: Yuma 3 / Yuma 4, never
 // the shared-input sweep scan)
 // A strided history (hist_strided) runs the dense history's shape at every
 // stride, in that shape's HS instantiation ("Strided bond history").
+// A bfloat16 history (BondArgs::hbf16; run_impl admits it for Yuma 3 / Yuma 4
+// in vector form without shared inputs, where a history is written from the
+// wide or the 64-miner-tile shape only) runs the same two shapes with
+// HT = __bf16 ("bfloat16 bond history").
 template <int VARIANT, bool VEC, typename WT>
 int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
   const bool hist = A.B_hist != nullptr;
   const bool hs = hist && yk::hist_strided(A);
+  if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3) {
+    if (A.hbf16) {
+      return with_bool(hs, [&](auto HS) {
+        constexpr bool kHs = decltype(HS)::value;
+        if (A.M >= 1024)
+          return launch_elem_shape<WT, VARIANT, 2, true, kWideP, true, true, 512, 1024, yk::DP_VQ, false, kHs,
+                                   __bf16>(st, A);
+        return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, __bf16>(st, A);
+      });
+    }
+  }
   if constexpr (VEC) {
     if (hist && A.M >= 1024) {
       constexpr int P = VARIANT <= YUMA_VARIANT_YUMA2 ? kWidePCn : kWideP;
@@ -5698,6 +5742,18 @@ bool u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* o
   return true;
 }
 
+// Whether a run with these arguments and YUMA_RUN_HIST_BF16 writes its bond
+// history as bfloat16 (yuma_hist_bf16_native): the element-wise variants in
+// vector form, at any validator count (one scan serves them all), a history
+// requested, no shared inputs (k_bonds_grp writes fp32 only). Only these
+// scans are instantiated for a __bf16 history.
+bool hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || V < 1 || M < 1 || V > YUMA_MAX_VALIDATORS || (M % 4) != 0) return false;
+  if (flags & YUMA_RUN_SHARED_INPUTS) return false;
+  return out != nullptr && out->B_hist != nullptr;
+}
+
 // What run_impl and shard_stage_impl decide alike.
 int check_sizes(int variant, int N, int E, int V, int M) {
   if (variant < 0 || variant > 4) return fail(YUMA_EINVAL, "unknown variant %d", variant);
@@ -5711,13 +5767,16 @@ int check_sizes(int variant, int N, int E, int V, int M) {
 
 // Vector form: a lane's 4 columns are one vector load (16 bytes of fp32, 8 of
 // uint16) of W and of every fp32 matrix read or written
+// (8 bytes of a bfloat16 history: hist_bf16)
 template <typename WT>
-bool vector_form(int M, const WT* W, const float* B_init, const float* Wprev_init, const yuma_outputs_t* out) {
+bool vector_form(int M, const WT* W, const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                 bool hist_bf16 = false) {
   if ((M % 4) != 0 || ((uintptr_t)W & (4 * sizeof(WT) - 1)) != 0) return false;
   const float* mats[] = {B_init, Wprev_init, out->Wn, out->Wc, out->Wb, out->B_inst,
-                         out->B_hist, out->B_final};
+                         hist_bf16 ? nullptr : out->B_hist, out->B_final};
   for (const float* p : mats)
     if (p != nullptr && !aligned16(p)) return false;
+  if (hist_bf16 && ((uintptr_t)out->B_hist & 7) != 0) return false;
   return true;
 }
 
@@ -5803,7 +5862,8 @@ template <typename WT>
 int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, const WT* W,
              const float* S, const float* B_init, const float* Wprev_init,
              const yuma_outputs_t* out, void* workspace, size_t ws_bytes, int chunk,
-             void* stream, float* phase_ms = nullptr, int wsh = 0, int hist_stride = 1, int hist_first = 0) {
+             void* stream, float* phase_ms = nullptr, int wsh = 0, int hist_stride = 1, int hist_first = 0,
+             int hist_bf16 = 0) {
   constexpr bool U16 = std::is_same_v<WT, uint16_t>;
   static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
   if (const int err = check_sizes(variant, N, E, V, M)) return err;
@@ -5821,7 +5881,19 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
   const int tiles = (M + yk::kTileM - 1) / yk::kTileM;
   const RowCfg rc = row_cfg(V);
 
-  const bool vec = vector_form(M, W, B_init, Wprev_init, out);
+  const bool vec = vector_form(M, W, B_init, Wprev_init, out, hist_bf16 != 0);
+  if (hist_bf16) {  // before the first launch
+    if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
+    if (!hist_bf16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
+      return fail(YUMA_EUNSUPPORTED,
+                  "YUMA_RUN_HIST_BF16 is not native for variant=%d V=%d M=%d shared=%d (yuma_hist_bf16_native): "
+                  "run the fp32 history and convert it",
+                  variant, V, M, wsh);
+    if (!vec)
+      return fail(YUMA_EUNSUPPORTED,
+                  "YUMA_RUN_HIST_BF16 needs B_hist 8-byte aligned, W vector-aligned and the fp32 matrices "
+                  "16-byte aligned");
+  }
   if constexpr (U16) {  // before the first launch
     if (!u16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
       return fail(YUMA_EUNSUPPORTED,
@@ -5940,6 +6012,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
     A.t0 = c0;
     A.t1 = c1;
     A.wsh = wsh;
+    A.hbf16 = hist_bf16;
     {
       // the history countdown of this chunk (BondArgs::hnext): epochs count
       // from the run's epoch 0, so the slot follows the absolute epoch
@@ -6109,7 +6182,7 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
 
 }  // namespace
 
-constexpr int kRunFlags = YUMA_RUN_SHARED_INPUTS | YUMA_RUN_W_U16;
+constexpr int kRunFlags = YUMA_RUN_SHARED_INPUTS | YUMA_RUN_W_U16 | YUMA_RUN_HIST_BF16;
 
 namespace {
 // yuma_run_options_t checked and resolved: NULL is every default; stride 0 is 1.
@@ -6156,11 +6229,12 @@ int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int 
                 int chunk_epochs, int flags, void* stream, float* phase_ms) {
   if (flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
   const int wsh = (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
+  const int hbf = (flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
   if (flags & YUMA_RUN_W_U16)
     return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
-                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh);
+                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh, 1, 0, hbf);
   return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh);
+                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, 1, 0, hbf);
 }
 
 int yuma_run_opts(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
@@ -6170,12 +6244,13 @@ int yuma_run_opts(int variant, const yuma_params_t* params_dev, int N, int E, in
   RunOpts o;
   if (const int err = read_opts(opts, &o)) return err;
   const int wsh = (o.flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
+  const int hbf = (o.flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
   if (o.flags & YUMA_RUN_W_U16)
     return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
                     Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride,
-                    o.first);
+                    o.first, hbf);
   return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride, o.first);
+                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride, o.first, hbf);
 }
 
 int yuma_hist_slots(int E, int hist_stride, int hist_first) {
@@ -6187,6 +6262,10 @@ int yuma_hist_slots(int E, int hist_stride, int hist_first) {
 
 int yuma_u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
   return u16_native(variant, N, E, V, M, out, flags) ? 1 : 0;
+}
+
+int yuma_hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  return hist_bf16_native(variant, N, E, V, M, out, flags) ? 1 : 0;
 }
 
 int yuma_run_profiled(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
@@ -6242,6 +6321,13 @@ int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t
   // refused before the capture starts (run_impl would refuse it before its first launch)
   if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags))
     return fail(YUMA_EUNSUPPORTED, "YUMA_RUN_W_U16 is not native for these arguments (yuma_u16_native)");
+  const int hbf = (flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
+  if (hbf && out != nullptr) {  // (a null `out` is run_impl's to refuse)
+    if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
+    if (!hist_bf16_native(variant, N, E, V, M, out, flags))
+      return fail(YUMA_EUNSUPPORTED,
+                  "YUMA_RUN_HIST_BF16 is not native for these arguments (yuma_hist_bf16_native)");
+  }
   hipStream_t cs = nullptr;
   if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess)
     return fail(YUMA_EHIP, "capture stream creation failed");
@@ -6252,9 +6338,9 @@ int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t
   const int rc = (flags & YUMA_RUN_W_U16)
                      ? run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S,
                                 B_init, Wprev_init, out, workspace, workspace_bytes, chunk_epochs, cs,
-                                nullptr, wsh, o.stride, o.first)
+                                nullptr, wsh, o.stride, o.first, hbf)
                      : run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                                workspace_bytes, chunk_epochs, cs, nullptr, wsh, o.stride, o.first);
+                                workspace_bytes, chunk_epochs, cs, nullptr, wsh, o.stride, o.first, hbf);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(cs, &g);
   (void)hipStreamDestroy(cs);

@@ -36,6 +36,7 @@ FLAG_RESET_ALL_COLUMNS = 2  # the reset zeroes every column (reset_bonds_index N
 RESET_NONE, RESET_ALWAYS, RESET_IF_ZERO_CONSENSUS = range(3)
 RUN_SHARED_INPUTS = 1  # yuma_run_ex flags
 RUN_W_U16 = 2  # ... W holds uint16 elements (the on-chain weight format), read natively
+RUN_HIST_BF16 = 4  # ... B_hist holds bfloat16 elements, written by the bond scan
 LIQUID_OFF, LIQUID_QUANTILE, LIQUID_CONST_AB = range(3)
 OVR_HIGH, OVR_LOW, OVR_FORCE_Q99 = 1, 2, 4
 
@@ -182,6 +183,10 @@ def load_library(path: str | None = None):
         # test_host.py, whose pattern takes lower-case letters only)
         lib.yuma_u16_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
         lib.yuma_u16_native.restype = i32
+        # (outside EXPORTED_SYMBOLS for the same reason: the digits in its name)
+        if hasattr(lib, "yuma_hist_bf16_native"):  # (A/B libraries of older sources lack it)
+            lib.yuma_hist_bf16_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
+            lib.yuma_hist_bf16_native.restype = i32
         lib.yuma_epoch.argtypes = [i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]
         lib.yuma_epoch.restype = i32
         lib.yuma_shard_stage.argtypes = [i32, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp,
@@ -482,6 +487,18 @@ def u16_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = F
     return bool(load_library().yuma_u16_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
 
 
+def hist_bf16_native(variant: int, N: int, E: int, V: int, M: int, *, shared_inputs: bool = False,
+                     want_hist: bool = True) -> bool:
+    """Whether `run` with hist_dtype=torch.bfloat16 and these arguments has the
+    bond scan write the history as bfloat16 (yuma_hist_bf16_native; needs the
+    library, not a GPU): Yuma 3 / Yuma 4, any V, M % 4 == 0, no shared inputs,
+    a history wanted. Otherwise `run` converts an fp32 history on the device
+    and RunGraph refuses."""
+    outs = YumaOutputsC(B_hist=1 if want_hist else None)
+    flags = RUN_SHARED_INPUTS if shared_inputs else 0
+    return bool(load_library().yuma_hist_bf16_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
+
+
 def to_u16(W: torch.Tensor) -> torch.Tensor:
     """The on-chain max-upscale of float weights to 16 bits: per row (last
     dimension) round_half_even(w / rowmax * 65535), computed in float64; an
@@ -535,7 +552,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         workspace: torch.Tensor | None = None, out: dict | None = None,
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
-        hist_stride: int = 1, hist_first: int | None = None) -> RunResult:
+        hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -548,7 +565,20 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     state after the epochs hist_epochs(E, hist_stride, hist_first) only:
     B_hist is [n_hist, N, V, M], slice j bit-equal to the dense history's slice
     at RunResult.hist_epochs[j] (yuma_run_opts). hist_first=None is
-    hist_stride - 1. Stride 1 from epoch 0 is the dense history."""
+    hist_stride - 1. Stride 1 from epoch 0 is the dense history.
+    hist_dtype: None / torch.float32, or torch.bfloat16: B_hist is then
+    bfloat16, every element RNE(fp32 bond state); every other output keeps the
+    bits of the fp32-history run. Where hist_bf16_native holds (and B_hist is
+    8-byte aligned) the bond scan writes the 16-bit history itself
+    (YUMA_RUN_HIST_BF16, extra["hist_path"] == "bf16"); elsewhere the run
+    writes an fp32 history and converts it on the device (extra["hist_path"] ==
+    "f32"; a captured run raises EngineError instead). A caller's out["B_hist"]
+    must be bfloat16. For reading, not for resuming: resume from B_final."""
+    if hist_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"hist_dtype={hist_dtype} must be None, torch.float32 or torch.bfloat16")
+    h_bf16 = hist_dtype == torch.bfloat16
+    if h_bf16 and single_call:
+        raise ValueError("single_call (yuma_epoch) writes an fp32 history: no hist_dtype=torch.bfloat16")
     E, Nw, V, M = W.shape
     check_limits(V, M)
     dev = device()
@@ -598,6 +628,15 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     need("C", (E, N, M))
     need("I", (E, N, M))
     need("B_final", (N, V, M))
+    hist_user = o.get("B_hist") if h_bf16 else None  # the caller's bfloat16 buffer
+    if hist_user is not None and hist_user.dtype != torch.bfloat16:
+        raise ValueError(f"out['B_hist'] is {hist_user.dtype}, hist_dtype=torch.bfloat16 needs a bfloat16 tensor")
+    # (a history of no slots is a null pointer to the engine: nothing to write in either type)
+    hist_native = (h_bf16 and (want_hist or hist_user is not None) and len(h_epochs) > 0
+                   and hist_bf16_native(variant, N, E, V, M, shared_inputs=shared_inputs)
+                   and (hist_user is None or hist_user.data_ptr() % 8 == 0))
+    if want_hist and hist_native and hist_user is None:
+        o["B_hist"] = torch.empty((len(h_epochs), N, V, M), dtype=torch.bfloat16, device=dev)
     if want_hist:
         need("B_hist", (len(h_epochs), N, V, M))
     if o.get("B_hist") is not None:
@@ -614,6 +653,19 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         need(name, shapes[name])
     if "T" in o and "P" not in o:
         need("P", shapes["P"])
+    if hist_native:
+        # the scan's vector form, as the engine tests it: W and every fp32
+        # matrix on its vector alignment (an odd view sends the run to the
+        # scalar scan, which writes an fp32 history only)
+        mats = [B_init, Wprev_init] + [o.get(k) for k in ("B_final", "Wn", "Wc", "Wb", "B_inst")]
+        if W.data_ptr() % (8 if w_u16 else 16) or any(t is not None and t.data_ptr() % 16 for t in mats):
+            hist_native = False
+    if h_bf16 and o.get("B_hist") is not None and not hist_native:
+        if capture is not None:
+            raise EngineError("a captured run cannot convert an fp32 history: hist_dtype=torch.bfloat16 needs "
+                              "hist_bf16_native(variant, N, E, V, M), a stored epoch and vector-aligned buffers")
+        if o["B_hist"].dtype != torch.float32:  # the run's fp32 history, converted below
+            o["B_hist"] = torch.empty((len(h_epochs), N, V, M), dtype=torch.float32, device=dev)
     full = o.get("Tv") is not None
     nbytes = workspace_bytes(variant, N, E, V, M, full)
     if workspace is None or workspace.numel() < nbytes:
@@ -626,13 +678,14 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     if w_u16:
         # the fp32 matrices of the vector paths: a view at an odd offset sends
         # the fp32 run to its scalar loads, which the uint16 kernels lack
-        mats = [B_init, Wprev_init] + [o.get(k) for k in ("B_hist", "B_final")]
+        mats = [B_init, Wprev_init, o.get("B_final")] + ([] if hist_native else [o.get("B_hist")])
         if any(t is not None and t.data_ptr() % 16 for t in mats):
             w_u16 = False
             W = _as_dev(W, dev)
             args = args[:6] + (W.data_ptr(),) + args[7:]
-    if strided:  # yuma_run_opts / yuma_graph_create_opts: the history stride, with the run's flags
-        opts = YumaRunOptionsC(flags=(RUN_W_U16 if w_u16 else 0) | (RUN_SHARED_INPUTS if shared_inputs else 0),
+    if strided or hist_native:  # yuma_run_opts / yuma_graph_create_opts: the history options, with the run's flags
+        opts = YumaRunOptionsC(flags=(RUN_W_U16 if w_u16 else 0) | (RUN_SHARED_INPUTS if shared_inputs else 0)
+                               | (RUN_HIST_BF16 if hist_native else 0),
                                # (a stride of E or more stores one epoch at the most: int32 either way)
                                hist_stride=min(int(hist_stride), E), hist_first=h_epochs[0] if h_epochs else E)
         if capture is not None:
@@ -687,7 +740,10 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
     keep["w_path"] = "u16" if w_u16 else "f32"  # how W was read: natively as uint16, or as fp32
+    keep["hist_path"] = "bf16" if hist_native else "f32"  # how the scan wrote the history
     hist = o.get("B_hist")
+    if h_bf16 and hist is not None and not hist_native:  # the fp32 history, rounded to nearest even
+        hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)
     return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs)
 
 

@@ -92,21 +92,29 @@ def _reward_key(config: YumaConfig) -> tuple:
 
 
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
-                    want_incentives: bool = True, bonds_every: int = 1):
+                    want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
     bonds_every: each run's bonds list holds the bond states after the epochs
     engine.hist_epochs(E, bonds_every) only (every bonds_every-th epoch), in
     order; the engine stores no other (engine.run's hist_stride). Dividends
-    and incentives stay per epoch."""
+    and incentives stay per epoch.
+    bonds_dtype: None / torch.float32, or torch.bfloat16: the bonds tensors are
+    then bfloat16, each the fp32 bond state rounded to nearest even (engine.run's
+    hist_dtype: written as 16 bits by the bond scan where the engine can, half
+    the history's device memory and half the bytes of its copy to the host).
+    For reading and charting; dividends and incentives are unchanged."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
+    if bonds_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"bonds_dtype={bonds_dtype} must be None, torch.float32 or torch.bfloat16")
     # the result lists are thousands of fresh containers (the sheet: 1512
     # dividend lists): the cyclic collector would sweep the process's whole
     # heap several times while they are built; they hold no cycles
     with _no_cyclic_gc():
-        return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every))
+        return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every),
+                                bonds_dtype=bonds_dtype)
 
 
 @contextmanager
@@ -163,7 +171,7 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
-                     totals: bool = False, bonds_every: int = 1):
+                     totals: bool = False, bonds_every: int = 1, bonds_dtype=None):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -204,7 +212,8 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
             params.append(rec)
         W, S, S_host = _group_inputs([packed[k] for k in idx], E * V * M * len(idx))
         launched.append((E, V, idx, S_host, engine.run(variant, params, W, S, want_hist=want_bonds,
-                                                              hist_stride=bonds_every)))
+                                                              hist_stride=bonds_every,
+                                                              hist_dtype=bonds_dtype if want_bonds else None)))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
         hist = res.B_hist.cpu() if want_bonds else None
