@@ -254,6 +254,54 @@ int yuma_u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_
 int yuma_hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out,
                           int flags);
 
+/* ------------------------------------------------------------------------
+ * Input schedules: E epochs over K stored weight / stake slices.
+ *
+ * Simulated inputs are piecewise constant (every case of cases.py holds a
+ * handful of matrices for tens of epochs; a convergence study holds one for
+ * thousands). yuma_run_sched takes the K distinct slices once, W [K][N][V][M]
+ * (uint16 under YUMA_RUN_W_U16) and S [K][N][V], and a schedule sched_dev [E]
+ * in DEVICE memory: epoch t reads slice sched_dev[t]. Every output has the
+ * bits of yuma_run_opts on the expanded inputs W'[t] = W[sched[t]],
+ * S'[t] = S[sched[t]]: the per-epoch outputs stay [E][N][..], B_hist keeps its
+ * dense, strided or bfloat16 shape, reset_epoch stays an epoch index and the
+ * conditional reset reads the previous epoch's consensus; the result does not
+ * depend on chunk_epochs. Slices that no epoch references are allowed, and so
+ * is K > E. The run stores K instead of E slices of W and makes the three
+ * phase-1 passes over W (row sums, consensus, rank: pure functions of one
+ * slice) once per stored slice instead of once per epoch; a gather kernel
+ * copies their per-slice vectors into the per-epoch arrays, counted under
+ * YUMA_PHASE_INCENTIVE in phase_ms.
+ *
+ * Native (yuma_sched_native returns 1): Yuma 3 and Yuma 4 (scalar or liquid
+ * alpha, any reset mode), any V up to YUMA_MAX_VALIDATORS, M % 4 == 0 with
+ * the alignments YUMA_RUN_W_U16 states (the vector form), no
+ * YUMA_RUN_SHARED_INPUTS, none of Wn / Wc / Wb / B_inst / Tv / P / T
+ * requested. Combines with YUMA_RUN_W_U16 (where yuma_u16_native holds), the
+ * history stride and YUMA_RUN_HIST_BF16 (where yuma_hist_bf16_native holds)
+ * as the dense run does; `flags` of yuma_sched_native are the run's flags.
+ * Elsewhere the entry points return YUMA_EUNSUPPORTED before the first launch
+ * and the caller expands the inputs itself.
+ *
+ * The host cannot check a schedule in device memory without a
+ * synchronisation: every kernel that addresses memory through a schedule
+ * entry clamps it into [0, K) first, so a bad schedule gives unspecified
+ * numbers and never an access outside W and S. K < 1, a NULL sched_dev and
+ * negative option fields return YUMA_EINVAL before the first launch. The
+ * workspace is yuma_workspace_bytes_sched (>= yuma_workspace_bytes for the
+ * same E, growing with K). A graph re-reads the schedule at every replay:
+ * rewrite it in place between replays like any other input.
+ * ---------------------------------------------------------------------- */
+size_t yuma_workspace_bytes_sched(int variant, int N, int E, int K, int V, int M, int full_outputs);
+int yuma_run_sched(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                   const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                   const float* Wprev_init, const yuma_outputs_t* out, void* workspace,
+                   size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts,
+                   void* stream, float* phase_ms);
+/* Host only, needs no GPU; of `out` it reads only which pointers are non-NULL. */
+int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma_outputs_t* out,
+                      int flags);
+
 /* hipGraph form of yuma_run: the whole multi-epoch run (every phase of every
  * chunk, no host work between them) captured once into a HIP graph and
  * replayed with one hipGraphLaunch. The arguments are those of yuma_run and
@@ -279,6 +327,12 @@ int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t
                            const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                            void* workspace, size_t workspace_bytes, int chunk_epochs,
                            const yuma_run_options_t* opts);
+/* yuma_graph_create_opts under an input schedule (yuma_run_sched's arguments). */
+int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                            int E, int K, int V, int M, const float* W, const float* S,
+                            const int32_t* sched_dev, const float* B_init, const float* Wprev_init,
+                            const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
+                            int chunk_epochs, const yuma_run_options_t* opts);
 /* Replay on `stream` (stream-ordered, no host synchronisation). */
 int yuma_graph_launch(yuma_graph_t graph, void* stream);
 /* Kernel nodes in the captured graph (diagnostics / tests). */

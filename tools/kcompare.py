@@ -48,6 +48,9 @@ def kernels(lib):
 
 
 def key(name):
+    # <..., HT, SC = false> takes conditional_t<SC, BondArgsSc, BondArgs>: the name of before the input
+    # schedules (SC = true, BondArgsSc: only in a library that has them)
+    name = re.sub(r"Lb0EEEvNSt11conditionalIXT\d+_ENS_10BondArgsScENS_8BondArgsEE4typeE$", TAIL, name)
     # <..., WT, HS, HT = float> ends in Lb0Ef / Lb1Ef; without HT the name ends in Lb0E / Lb1E
     if "k_bonds_elemI" in name and re.search(r"Lb[01]Ef" + TAIL + "$", name):
         return name[:-len("f" + TAIL)] + TAIL

@@ -3255,6 +3255,11 @@ struct BondArgs {
   int hbf16;
 };
 static_assert(sizeof(BondArgs) == 216, "hbf16 sits in the former tail padding: the argument block keeps its size");
+// ... under an input schedule (k_bonds_elem<.., SC = true>)
+struct BondArgsSc : BondArgs {
+  const int32_t* sched;  // [E] device memory: epoch t reads stored slice sched[t]
+  int K;                 // stored slices
+};
 __host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
   return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
 }
@@ -4057,9 +4062,21 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // dividend partials and Bstate are formed from the fp32 registers, so every
 // other output keeps the fp32-history run's bits. Only the two vector shapes
 // that write a history (wide, 64-miner tile) are instantiated for it.
+// SC: an input schedule (yuma_run_sched). W holds K stored slices and epoch t
+// reads slice sched[t]: the W address alone takes the schedule entry, every
+// other per-epoch read keeps slice = t N + n (k_sched_expand has gathered the
+// per-slice vectors into per-epoch arrays). The entry is block-uniform: it is
+// read through the constant address space (a scalar load, outside the vector
+// prefetch ring; the schedule is not written while a run is in flight),
+// clamped into [0, K) with scalar min / max, and read one fetch ahead so that
+// no fetch waits for it. BondArgs has no room for the two words: the SC
+// instantiations take BondArgsSc, the record with the two appended, and every
+// other instantiation keeps its argument block and its code.
 template <int VARIANT, int R, bool VEC, int P, bool VECI, bool NT = false, int BS = 256, int CB = 64,
-          int DPL = DP_TV, bool RQ = false, typename WT = float, bool HS = false, typename HT = float>
-__global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
+          int DPL = DP_TV, bool RQ = false, typename WT = float, bool HS = false, typename HT = float,
+          bool SC = false>
+__global__ __launch_bounds__(BS, 1) void k_bonds_elem(std::conditional_t<SC, BondArgsSc, BondArgs> A) {
+  static_assert(!SC || (VEC && VARIANT >= YUMA_VARIANT_YUMA3), "input schedules: Yuma 3 / Yuma 4, vector form");
   static_assert(std::is_same_v<HT, float> || (std::is_same_v<HT, __bf16> && NT && VEC && !RQ &&
                                               VARIANT >= YUMA_VARIANT_YUMA3),
                 "bf16 history: Yuma 3 / Yuma 4, vector form, non-temporal stores");
@@ -4161,7 +4178,18 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
   // a duplicate scenario of a rank class reads its representative's column sums
   // (the rank pass skips duplicate slices; k_incentive copies R, not csb / csr)
   const int ncs = (COLNORM && A.csrep != nullptr) ? A.csrep[n] : n;
-  auto fetch = [&](int k, int t) {
+  // SC: the stored slice of epoch t (t clamped to the launch's last epoch, so
+  // the read-ahead stays inside the schedule's E entries)
+  auto sched_at = [&](int t) -> int {
+    if constexpr (SC) {
+      typedef const __attribute__((address_space(4))) int32_t* cptr;
+      const int tt = __builtin_amdgcn_readfirstlane(min(t, A.t1 - 1));
+      return min(max(__builtin_amdgcn_readfirstlane(((cptr)A.sched)[tt]), 0), A.K - 1);
+    } else {
+      return 0;
+    }
+  };
+  auto fetch = [&](int k, int t, int sk) {
     const long long slice = (long long)t * N + n;
     const long long cslice = (long long)t * N + ncs;
 #pragma unroll
@@ -4170,7 +4198,10 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
       // the one-row history-less scan streams each W slice exactly once
       // (rowsum / consensus / rank read it in their own launches): non-
       // temporal loads (c4 bonds 1.63 -> 1.50 ms, same box)
-      load4c<VEC, DPL == DP_QTE>(Wa + (A.wsh ? (long long)t : slice) * VM, rr, V, m, M, rw[k][i]);
+      if constexpr (SC)  // the stored slice of this epoch
+        load4c<VEC, DPL == DP_QTE>(Wa + ((long long)sk * N + n) * VM, rr, V, m, M, rw[k][i]);
+      else
+        load4c<VEC, DPL == DP_QTE>(Wa + (A.wsh ? (long long)t : slice) * VM, rr, V, m, M, rw[k][i]);
       rd[k][i] = A.rsd[slice * V + rr];
       rsn[k][i] = A.sn[slice * V + rr];
       // RQ: the screened reciprocal alone (rq4.y). (One 16-byte rq4 load for
@@ -4203,7 +4234,8 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
   long long hsl = HS ? (long long)A.hslot * N + n : 0;
 #pragma unroll
   for (int k = 0; k < P; ++k)
-    if (A.t0 + k < A.t1) fetch(k, A.t0 + k);
+    if (A.t0 + k < A.t1) fetch(k, A.t0 + k, sched_at(A.t0 + k));
+  int snext = sched_at(A.t0 + P);  // SC: the slice of the next epoch to fetch
 
   for (int tb = A.t0; tb < A.t1; tb += P) {
 #pragma unroll
@@ -4413,13 +4445,65 @@ __global__ __launch_bounds__(BS, 1) void k_bonds_elem(BondArgs A) {
       }
       has_old = true;
       if (YUMA2) have_wp = true;
-      if (t + P < A.t1) fetch(k, t + P);
+      if (t + P < A.t1) {
+        fetch(k, t + P, snext);
+        if constexpr (SC) snext = sched_at(t + P + 1);
+      }
     }
   }
 #pragma unroll
   for (int i = 0; i < R; ++i) {
     const int row = row0 + G * i;
     if (row < V) store4<VEC>(A.Bstate + n * VM + (long long)row * M, m, M, B[i]);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Input schedules (yuma_run_sched): phase 1 ran over the K stored slices into
+// a staging set of per-slice vectors; this gathers them into the per-epoch
+// arrays that the bond scan, k_finalize and the outputs read. One block per
+// (epoch, scenario, array): epoch t of scenario n takes stored slice
+// clamp(sched[t]) N + n. The schedule entry is block-uniform and clamped into
+// [0, K) before it addresses anything, so a bad schedule gives unspecified
+// numbers and no access outside the staging set. Rows move as 16-byte vectors
+// where both ends are 16-byte aligned and the length is a multiple of 4.
+// liquid: the array is written for liquid scenarios only (bond_alpha; the
+// dense run leaves it untouched elsewhere).
+// ---------------------------------------------------------------------------
+constexpr int kExpandArrays = 8;
+struct ExpandArgs {
+  const float* src[kExpandArrays];  // [K][N][len]
+  float* dst[kExpandArrays];        // [E][N][len]
+  int len[kExpandArrays];
+  int liquid[kExpandArrays];
+  const int32_t* sched;             // [E]
+  const yuma_params_t* prm;         // [N]
+  int narr, N, K;
+};
+__global__ __launch_bounds__(256) void k_sched_expand(ExpandArgs X) {
+  const int a = blockIdx.x % X.narr;
+  const long long slice = blockIdx.x / X.narr;  // t N + n
+  const int t = (int)(slice / X.N), n = (int)(slice % X.N);
+  const float* src = nullptr;
+  float* dst = nullptr;
+  int len = 0, liq = 0;
+#pragma unroll
+  for (int i = 0; i < kExpandArrays; ++i)  // (no dynamic index into the argument block)
+    if (i == a) {
+      src = X.src[i];
+      dst = X.dst[i];
+      len = X.len[i];
+      liq = X.liquid[i];
+    }
+  if (liq && X.prm[n].liquid_mode == YUMA_LIQUID_OFF) return;
+  const int k = min(max(__builtin_amdgcn_readfirstlane(X.sched[t]), 0), X.K - 1);
+  src += ((long long)k * X.N + n) * len;
+  dst += slice * len;
+  if ((len & 3) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
+    for (int i = threadIdx.x; i < (len >> 2); i += 256)
+      reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
+  } else {
+    for (int i = threadIdx.x; i < len; i += 256) dst[i] = src[i];
   }
 }
 
@@ -5238,7 +5322,10 @@ size_t partial_tiles(int variant, int M) {
 
 int dte_stride(int E) { return (E + 15) & ~15; }
 
-Workspace carve(char* base, int variant, int N, int E, int V, int M, int full) {
+// stage: the staging set of an input schedule (run_impl): phase 1's per-slice
+// vectors for E = K stored slices, without what only the bond scan and
+// k_finalize use (dividend partials, the bond state)
+Workspace carve(char* base, int variant, int N, int E, int V, int M, int full, bool stage = false) {
   Workspace w{};
   const size_t S = (size_t)E * N;
   const size_t tiles = (size_t)(M + yk::kTileM - 1) / yk::kTileM;
@@ -5261,12 +5348,12 @@ Workspace carve(char* base, int variant, int N, int E, int V, int M, int full) {
   w.rpart = (float*)take(S * tiles * 4);
   // DP_QTE pads each (scenario, quad, row) epoch series to a multiple of 16
   const size_t dp_te = (size_t)N * yk::dp_quads((int)tiles) * V * (size_t)dte_stride(E);
-  w.dpart = (float*)take(std::max(S * partial_tiles(variant, M) * V, dp_te) * 4);
-  w.dsum = (float*)take(S * V * 4);
+  w.dpart = stage ? nullptr : (float*)take(std::max(S * partial_tiles(variant, M) * V, dp_te) * 4);
+  w.dsum = stage ? nullptr : (float*)take(S * V * 4);
   w.scal = (float*)take(S * 8 * 4);
   w.tvc = full ? (float*)take(S * tiles * V * 4) : nullptr;
   w.tvn = full ? (float*)take(S * tiles * V * 4) : nullptr;
-  w.Bstate = (float*)take((size_t)N * V * M * 4);
+  w.Bstate = stage ? nullptr : (float*)take((size_t)N * V * M * 4);
   w.sumc_f = (float*)take(S * 4);
   w.sumc_d = (double*)take(S * 8);
   w.crep = (int*)take((size_t)N * 4);
@@ -5603,14 +5690,23 @@ constexpr int kScanGroup = 4;  // scenarios per block of the shared-input scan
 // 0.985-0.997 -> 0.916-0.923; profiles/r05/ab_elem_rq.txt)
 constexpr bool kElemRq(int variant, bool hist) { return hist ? variant <= YUMA_VARIANT_YUMA2 : true; }
 int bonds_rows(bool vec, bool hist, bool wsh) { return vec && (hist || wsh) ? 2 : 1; }
+// sched (with SC): the input schedule and its K stored slices (BondArgsSc)
 template <typename WT, int VARIANT, int R, bool VEC, int P, bool VECI, bool NT, int BS, int CB, int DPL,
-          bool RQ = false, bool HS = false, typename HT = float>
-int launch_elem_shape(hipStream_t st, yk::BondArgs& A) {
+          bool RQ = false, bool HS = false, typename HT = float, bool SC = false>
+int launch_elem_shape(hipStream_t st, yk::BondArgs& A, const int32_t* sched = nullptr, int K = 0) {
   constexpr int G = BS / (CB / 4);
   A.rowblocks = (A.V + G * R - 1) / (G * R);
   A.cblocks = (A.M + CB - 1) / CB;
   const long long nblocks = (long long)A.N * A.rowblocks * A.cblocks;
-  YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS, HT>), nblocks, BS, st, A);
+  if constexpr (SC) {
+    yk::BondArgsSc As{};
+    static_cast<yk::BondArgs&>(As) = A;
+    As.sched = sched;
+    As.K = K;
+    YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS, HT, true>), nblocks, BS, st,
+              As);
+  } else
+    YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS, HT>), nblocks, BS, st, A);
   return DPL;
 }
 // WT: the element type A.W addresses (uint16 weights: Yuma 3 / Yuma 4, never
@@ -5689,6 +5785,43 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
   });
 }
 
+// The scan under an input schedule (yuma_sched_native: Yuma 3 / Yuma 4, vector
+// form, no shared inputs, k_rowsum's reciprocals at hand): launch_bonds_elem's
+// choice of shape for such a run, decision for decision, in the SC
+// instantiations -- the bfloat16 and fp32 history from the wide or the
+// 64-miner-tile shape (dense or strided), the history-less forms with the
+// screened reciprocal.
+template <int VARIANT, typename WT>
+int launch_bonds_elem_sc(hipStream_t st, yk::BondArgs& A, const int32_t* sched, int K) {
+  const bool hist = A.B_hist != nullptr;
+  const bool hs = hist && yk::hist_strided(A);
+  if (A.hbf16)
+    return with_bool(hs, [&](auto HS) {
+      constexpr bool kHs = decltype(HS)::value;
+      if (A.M >= 1024)
+        return launch_elem_shape<WT, VARIANT, 2, true, kWideP, true, true, 512, 1024, yk::DP_VQ, false, kHs, __bf16,
+                                 true>(st, A, sched, K);
+      return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, __bf16, true>(
+          st, A, sched, K);
+    });
+  if (!hist) {
+    const long long blocks_r2 = (long long)A.N * ((A.V + 7) / 8) * ((A.M + 255) / 256);
+    if (blocks_r2 >= 4096)
+      return launch_elem_shape<WT, VARIANT, 2, true, kNoHistP2, true, false, 256, 256, yk::DP_QTE, true, false, float,
+                               true>(st, A, sched, K);
+    return launch_elem_shape<WT, VARIANT, 1, true, 4, true, false, 256, 256, yk::DP_QTE, true, false, float, true>(
+        st, A, sched, K);
+  }
+  return with_bool(hs, [&](auto HS) {
+    constexpr bool kHs = decltype(HS)::value;
+    if (A.M >= 1024)
+      return launch_elem_shape<WT, VARIANT, 2, true, kWideP, true, true, 512, 1024, yk::DP_VQ, false, kHs, float,
+                               true>(st, A, sched, K);
+    return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, float, true>(
+        st, A, sched, K);
+  });
+}
+
 // Launch the bond scan for A.N scenarios over epochs [A.t0, A.t1); returns
 // the layout of the dividend partials it wrote (k_finalize / k_dsum read it).
 template <bool VEC>
@@ -5752,6 +5885,21 @@ bool hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_output
   if (N < 1 || E < 1 || V < 1 || M < 1 || V > YUMA_MAX_VALIDATORS || (M % 4) != 0) return false;
   if (flags & YUMA_RUN_SHARED_INPUTS) return false;
   return out != nullptr && out->B_hist != nullptr;
+}
+
+// Whether a run with these arguments takes an input schedule natively
+// (yuma_sched_native): the element-wise variants in vector form, at any
+// validator count, per-scenario inputs, none of the per-epoch matrices nor the
+// prerank / trust requested (the schedule path gathers per-slice vectors only).
+// With YUMA_RUN_W_U16 / YUMA_RUN_HIST_BF16 in `flags`, where those are native.
+bool sched_native(int variant, int N, int E, int K, int V, int M, const yuma_outputs_t* out, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || K < 1 || V < 1 || M < 1 || V > YUMA_MAX_VALIDATORS || (M % 4) != 0) return false;
+  if (flags & YUMA_RUN_SHARED_INPUTS) return false;
+  if (out != nullptr && (out->Wn || out->Wc || out->Wb || out->B_inst || out->Tv || out->P || out->T)) return false;
+  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags)) return false;
+  if ((flags & YUMA_RUN_HIST_BF16) && !hist_bf16_native(variant, N, E, V, M, out, flags)) return false;
+  return true;
 }
 
 // What run_impl and shard_stage_impl decide alike.
@@ -5863,25 +6011,45 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
              const float* S, const float* B_init, const float* Wprev_init,
              const yuma_outputs_t* out, void* workspace, size_t ws_bytes, int chunk,
              void* stream, float* phase_ms = nullptr, int wsh = 0, int hist_stride = 1, int hist_first = 0,
-             int hist_bf16 = 0) {
+             int hist_bf16 = 0, const int32_t* sched = nullptr, int K = 0) {
+  // sched (yuma_run_sched): W is [K][N][V][M], S [K][N][V], and epoch t reads
+  // stored slice sched[t] ([E], device memory). Phase 1 then runs once per
+  // stored slice into a staging set carved behind the E-epoch workspace, and
+  // k_sched_expand gathers its per-slice vectors into the per-epoch arrays;
+  // the bond scan, k_finalize and the output copies run per epoch as ever.
   constexpr bool U16 = std::is_same_v<WT, uint16_t>;
   static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
   if (const int err = check_sizes(variant, N, E, V, M)) return err;
   if ((M + yk::kTileM - 1) / yk::kTileM > yk::kMaxTiles) return fail(YUMA_EINVAL, "M too large");
   if (!prm || !W || !S || !out || !workspace)
     return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
+  if (sched != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
   const int full = out->Tv != nullptr;
   // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
   // params live in device memory, so the Python marshaller enforces it.
   Workspace ws = carve((char*)workspace, variant, N, E, V, M, full);
-  if (ws.bytes > ws_bytes)
+  Workspace wk{};  // the staging set of the K stored slices
+  if (sched != nullptr) wk = carve((char*)workspace + ws.bytes, variant, N, K, V, M, 0, true);
+  if (ws.bytes + wk.bytes > ws_bytes)
     return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)",
-                ws_bytes, ws.bytes, full);
+                ws_bytes, ws.bytes + wk.bytes, full);
   hipStream_t st = (hipStream_t)stream;
   const int tiles = (M + yk::kTileM - 1) / yk::kTileM;
   const RowCfg rc = row_cfg(V);
 
   const bool vec = vector_form(M, W, B_init, Wprev_init, out, hist_bf16 != 0);
+  if (sched != nullptr) {  // before the first launch (the uint16 / bfloat16 tests of their own follow)
+    const int f = wsh ? YUMA_RUN_SHARED_INPUTS : 0;
+    if (!sched_native(variant, N, E, K, V, M, out, f))
+      return fail(YUMA_EUNSUPPORTED,
+                  "an input schedule is not native for variant=%d V=%d M=%d flags=0x%x or the requested outputs "
+                  "(yuma_sched_native): expand W and S to one slice per epoch",
+                  variant, V, M, f);
+    if (!vec)
+      return fail(YUMA_EUNSUPPORTED,
+                  "an input schedule (yuma_sched_native) needs the vector form: W vector-aligned and the fp32 "
+                  "matrices 16-byte aligned");
+  }
   if (hist_bf16) {  // before the first launch
     if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
     if (!hist_bf16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
@@ -5914,7 +6082,6 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
   };
 
   const Bufs buf = pick_bufs(out, ws);
-  float *const C = buf.C, *const I = buf.I, *const Rr = buf.R, *const ba_buf = buf.ba;
 
   // one chunk by default: phase 1 of every epoch, then one bond scan
   if (chunk <= 0 || chunk > E) chunk = E;
@@ -5947,8 +6114,10 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
   tm.ms = phase_ms;
   tm.st = st;
 
-  for (int c0 = 0; c0 < E; c0 += chunk) {
-    const int c1 = c0 + chunk < E ? c0 + chunk : E;
+  // Phase 1 of the input slices [c0, c1) into the per-slice vectors of w1 / b1:
+  // the run's own (a slice per epoch), or an input schedule's staging set
+  auto phase1 = [&](const Workspace& w1, const Bufs& b1, int c0, int c1) {
+    float *const C = b1.C, *const I = b1.I, *const Rr = b1.R, *const ba_buf = b1.ba;
     const long long s0 = (long long)c0 * N;
     const long long ns = (long long)(c1 - c0) * N;
     {
@@ -5963,7 +6132,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
         with_bool(wide, [&](auto WIDE) {  // a block per row, or per 4 rows
           const int rb = wide ? V : rowblocks4;
           YK_LAUNCH((yk::k_rowsum<decltype(VEC)::value, decltype(WIDE)::value, WT>), rs_in * rb, 256, st, W, S, V,
-                    M, rs_s0, rb, ws.rsd, ws.sn, 0, ws.sx, fan, ws.rq4);
+                    M, rs_s0, rb, w1.rsd, w1.sn, 0, w1.sx, fan, w1.rq4);
         });
       });
       tm.mark(YUMA_PHASE_CONSENSUS);
@@ -5973,36 +6142,75 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
           if (mc) {
             const int G = N < yk::kMcGroups ? N : yk::kMcGroups;
             const long long nb = (long long)(c1 - c0) * tiles * G;
-            launch_consensus_mc<kVec>(rc, nb, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, c0, tiles, ws.craw,
+            launch_consensus_mc<kVec>(rc, nb, st, W, w1.rsd, w1.sn, w1.sx, prm, N, V, M, c0, tiles, w1.craw,
                                       ws.clist, G);
             return;
           }
         }
-        launch_consensus<kVec>(rc, ns * tiles, st, W, ws.rsd, ws.sn, ws.sx, prm, N, V, M, s0, tiles, ws.craw,
-                               out->P, wsh, crep, kVec ? ws.rq4 : nullptr);
+        launch_consensus<kVec>(rc, ns * tiles, st, W, w1.rsd, w1.sn, w1.sx, prm, N, V, M, s0, tiles, w1.craw,
+                               out->P, wsh, crep, kVec ? w1.rq4 : nullptr);
       });
       tm.mark(YUMA_PHASE_QUANTISE);
-      YK_LAUNCH(yk::k_quantise<256>, ns, 256, st, ws.craw, prm, variant, N, M, s0, C, ws.qlev,
-                ba_buf, ws.scal, nullptr, nullptr, 0, crep);
+      YK_LAUNCH(yk::k_quantise<256>, ns, 256, st, w1.craw, prm, variant, N, M, s0, C, w1.qlev,
+                ba_buf, w1.scal, nullptr, nullptr, 0, crep);
       tm.mark(YUMA_PHASE_RANK);
       // the multi-class rank walks the consensus classes' list: only when the
       // rank classes are those classes (no bond column sums) and the streaming
       // rank of <= 1024 validators on 64-miner tiles would run
       const int* rlist = (mc && rcrep == crep && csb == nullptr && M < 16384) ? ws.clist : nullptr;
       if constexpr (U16)
-        launch_rank<true>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, N, V, M, s0, tiles, Rr, ws.rpart);
+        launch_rank<true>(rc, ns * tiles, st, W, w1.rsd, w1.sn, C, N, V, M, s0, tiles, Rr, w1.rpart);
       else
         with_bool(vec, [&](auto VEC) {
-          launch_rank<decltype(VEC)::value>(rc, ns * tiles, st, W, ws.rsd, ws.sn, C, Wprev_init,
-                                            variant == YUMA_VARIANT_YUMA2, N, V, M, s0, tiles, Rr, ws.rpart,
-                                            out->Wn, out->Wc, ws.tvc, ws.tvn, wsh, rcrep, csb, ws.csr, prm, rlist);
+          launch_rank<decltype(VEC)::value>(rc, ns * tiles, st, W, w1.rsd, w1.sn, C, Wprev_init,
+                                            variant == YUMA_VARIANT_YUMA2, N, V, M, s0, tiles, Rr, w1.rpart,
+                                            out->Wn, out->Wc, w1.tvc, w1.tvn, wsh, rcrep, csb, w1.csr, prm, rlist);
         });
     }
     tm.mark(YUMA_PHASE_INCENTIVE);
     const int ich = (M + yk::kIncCols - 1) / yk::kIncCols;
-    YK_LAUNCH(yk::k_incentive, ns * ich, 256, st, Rr, ws.rpart, out->P, M, s0, tiles, I,
-              out->P ? out->T : nullptr, ws.scal, nullptr, rcrep, N, ich, incentive_v4(M, Rr, I, out),
+    YK_LAUNCH(yk::k_incentive, ns * ich, 256, st, Rr, w1.rpart, out->P, M, s0, tiles, I,
+              out->P ? out->T : nullptr, w1.scal, nullptr, rcrep, N, ich, incentive_v4(M, Rr, I, out),
               (out->R != nullptr || variant == YUMA_VARIANT_RUST) ? 1 : 0);
+  };
+
+  if (sched != nullptr) {
+    // once per stored slice, in batches of the run's chunk size, then the gather
+    const Bufs kb{wk.C, wk.I, wk.R, nullptr, wk.ba};
+    const int kchunk = chunk < K ? chunk : K;
+    for (int k0 = 0; k0 < K; k0 += kchunk) phase1(wk, kb, k0, k0 + kchunk < K ? k0 + kchunk : K);
+    // (counted under YUMA_PHASE_INCENTIVE, the phase it follows)
+    yk::ExpandArgs X{};
+    int na = 0;
+    auto arr = [&](const float* src, float* dst, int len, int liquid) {
+      X.src[na] = src;
+      X.dst[na] = dst;
+      X.len[na] = len;
+      X.liquid[na] = liquid;
+      ++na;
+    };
+    arr(wk.rsd, ws.rsd, V, 0);
+    arr(wk.sn, ws.sn, V, 0);
+    arr(reinterpret_cast<const float*>(wk.rq4), reinterpret_cast<float*>(ws.rq4), 4 * V, 0);
+    arr(wk.C, buf.C, M, 0);
+    arr(wk.I, buf.I, M, 0);
+    arr(wk.ba, buf.ba, M, 1);
+    arr(wk.scal, ws.scal, 8, 0);
+    if (out->R != nullptr) arr(wk.R, out->R, M, 0);
+    static_assert(yk::kExpandArrays >= 8, "k_sched_expand's argument block holds every gathered array");
+    X.sched = sched;
+    X.prm = prm;
+    X.narr = na;
+    X.N = N;
+    X.K = K;
+    YK_LAUNCH(yk::k_sched_expand, (long long)E * N * na, 256, st, X);
+  }
+
+  for (int c0 = 0; c0 < E; c0 += chunk) {
+    const int c1 = c0 + chunk < E ? c0 + chunk : E;
+    const long long s0 = (long long)c0 * N;
+    const long long ns = (long long)(c1 - c0) * N;
+    if (sched == nullptr) phase1(ws, buf, c0, c1);
 
     // (A.W: the scan is launched for WT)
     yk::BondArgs A = bond_args(reinterpret_cast<const float*>(W), ws, buf, prm, B_init, Wprev_init, out, csb, N,
@@ -6025,7 +6233,10 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
     tm.mark(YUMA_PHASE_BONDS);
     int ptiles = tiles;
     int dpl;
-    if constexpr (U16)
+    if (sched != nullptr)  // (Yuma 3 / Yuma 4 in vector form: checked above)
+      dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem_sc<YUMA_VARIANT_YUMA3, WT>(st, A, sched, K)
+                                          : launch_bonds_elem_sc<YUMA_VARIANT_YUMA4, WT>(st, A, sched, K);
+    else if constexpr (U16)
       dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem<YUMA_VARIANT_YUMA3, true, WT>(st, A)
                                           : launch_bonds_elem<YUMA_VARIANT_YUMA4, true, WT>(st, A);
     else
@@ -6201,12 +6412,84 @@ int read_opts(const yuma_run_options_t* o, RunOpts* r) {
   *r = RunOpts{o->flags, o->hist_stride == 0 ? 1 : o->hist_stride, o->hist_first};
   return YUMA_OK;
 }
+
+// run_impl for resolved options, in the weight type the flags name. sched:
+// the input schedule of yuma_run_sched (K stored slices), or NULL.
+int run_with(const RunOpts& o, int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
+             const float* W, const float* S, const float* B_init, const float* Wprev_init,
+             const yuma_outputs_t* out, void* workspace, size_t workspace_bytes, int chunk_epochs, void* stream,
+             float* phase_ms, const int32_t* sched = nullptr, int K = 0) {
+  const int wsh = (o.flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
+  const int hbf = (o.flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
+  if (o.flags & YUMA_RUN_W_U16)
+    return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
+                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride,
+                    o.first, hbf, sched, K);
+  return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride, o.first, hbf, sched, K);
+}
+
+// What yuma_run_sched and yuma_graph_create_sched refuse alike, before any launch.
+int check_sched(const int32_t* sched_dev, int K) {
+  if (K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
+  if (sched_dev == nullptr) return fail(YUMA_EINVAL, "the schedule pointer is NULL");
+  return YUMA_OK;
+}
 }  // namespace
 
 struct yuma_graph {
   hipGraph_t graph;
   hipGraphExec_t exec;
 };
+
+namespace {
+// The capture behind every yuma_graph_create*: run_with on a capture stream.
+int graph_create_impl(yuma_graph_t* graph, const RunOpts& o, int variant, const yuma_params_t* params_dev, int N,
+                      int E, int V, int M, const float* W, const float* S, const float* B_init,
+                      const float* Wprev_init, const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
+                      int chunk_epochs, const int32_t* sched = nullptr, int K = 0) {
+  const int flags = o.flags;
+  if (graph == nullptr) return fail(YUMA_EINVAL, "graph handle pointer is NULL");
+  *graph = nullptr;
+  // refused before the capture starts (run_impl would refuse it before its first launch)
+  if (sched != nullptr && !sched_native(variant, N, E, K, V, M, out, flags))
+    return fail(YUMA_EUNSUPPORTED, "an input schedule is not native for these arguments (yuma_sched_native)");
+  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags))
+    return fail(YUMA_EUNSUPPORTED, "YUMA_RUN_W_U16 is not native for these arguments (yuma_u16_native)");
+  const int hbf = (flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
+  if (hbf && out != nullptr) {  // (a null `out` is run_impl's to refuse)
+    if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
+    if (!hist_bf16_native(variant, N, E, V, M, out, flags))
+      return fail(YUMA_EUNSUPPORTED,
+                  "YUMA_RUN_HIST_BF16 is not native for these arguments (yuma_hist_bf16_native)");
+  }
+  hipStream_t cs = nullptr;
+  if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess)
+    return fail(YUMA_EHIP, "capture stream creation failed");
+  if (hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed) != hipSuccess) {
+    (void)hipStreamDestroy(cs);
+    return fail(YUMA_EHIP, "hipStreamBeginCapture failed");
+  }
+  const int rc = run_with(o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                          workspace_bytes, chunk_epochs, cs, nullptr, sched, K);
+  hipGraph_t g = nullptr;
+  const hipError_t ec = hipStreamEndCapture(cs, &g);
+  (void)hipStreamDestroy(cs);
+  if (rc != YUMA_OK) {
+    if (g) (void)hipGraphDestroy(g);
+    return rc;  // run_impl's message stands
+  }
+  if (ec != hipSuccess || g == nullptr)
+    return fail(YUMA_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ec));
+  hipGraphExec_t x = nullptr;
+  if (hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
+    (void)hipGraphDestroy(g);
+    return fail(YUMA_EHIP, "hipGraphInstantiate failed");
+  }
+  *graph = new yuma_graph{g, x};
+  return YUMA_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -6243,14 +6526,29 @@ int yuma_run_opts(int variant, const yuma_params_t* params_dev, int N, int E, in
                   int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms) {
   RunOpts o;
   if (const int err = read_opts(opts, &o)) return err;
-  const int wsh = (o.flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
-  const int hbf = (o.flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
-  if (o.flags & YUMA_RUN_W_U16)
-    return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
-                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride,
-                    o.first, hbf);
-  return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride, o.first, hbf);
+  return run_with(o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+                  chunk_epochs, stream, phase_ms);
+}
+
+size_t yuma_workspace_bytes_sched(int variant, int N, int E, int K, int V, int M, int full_outputs) {
+  if (N < 1 || E < 1 || K < 1 || V < 1 || M < 1) return 0;
+  return carve(nullptr, variant, N, E, V, M, full_outputs).bytes +
+         carve(nullptr, variant, N, K, V, M, 0, true).bytes;
+}
+
+int yuma_run_sched(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                   const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                   const float* Wprev_init, const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
+                   int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms) {
+  RunOpts o;
+  if (const int err = read_opts(opts, &o)) return err;
+  if (const int err = check_sched(sched_dev, K)) return err;
+  return run_with(o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+                  chunk_epochs, stream, phase_ms, sched_dev, K);
+}
+
+int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma_outputs_t* out, int flags) {
+  return sched_native(variant, N, E, K, V, M, out, flags) ? 1 : 0;
 }
 
 int yuma_hist_slots(int E, int hist_stride, int hist_first) {
@@ -6314,49 +6612,20 @@ int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t
                            const yuma_run_options_t* opts) {
   RunOpts o;
   if (const int err = read_opts(opts, &o)) return err;
-  const int flags = o.flags;
-  if (graph == nullptr) return fail(YUMA_EINVAL, "graph handle pointer is NULL");
-  *graph = nullptr;
-  const int wsh = (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
-  // refused before the capture starts (run_impl would refuse it before its first launch)
-  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags))
-    return fail(YUMA_EUNSUPPORTED, "YUMA_RUN_W_U16 is not native for these arguments (yuma_u16_native)");
-  const int hbf = (flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
-  if (hbf && out != nullptr) {  // (a null `out` is run_impl's to refuse)
-    if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
-    if (!hist_bf16_native(variant, N, E, V, M, out, flags))
-      return fail(YUMA_EUNSUPPORTED,
-                  "YUMA_RUN_HIST_BF16 is not native for these arguments (yuma_hist_bf16_native)");
-  }
-  hipStream_t cs = nullptr;
-  if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess)
-    return fail(YUMA_EHIP, "capture stream creation failed");
-  if (hipStreamBeginCapture(cs, hipStreamCaptureModeRelaxed) != hipSuccess) {
-    (void)hipStreamDestroy(cs);
-    return fail(YUMA_EHIP, "hipStreamBeginCapture failed");
-  }
-  const int rc = (flags & YUMA_RUN_W_U16)
-                     ? run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S,
-                                B_init, Wprev_init, out, workspace, workspace_bytes, chunk_epochs, cs,
-                                nullptr, wsh, o.stride, o.first, hbf)
-                     : run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                                workspace_bytes, chunk_epochs, cs, nullptr, wsh, o.stride, o.first, hbf);
-  hipGraph_t g = nullptr;
-  const hipError_t ec = hipStreamEndCapture(cs, &g);
-  (void)hipStreamDestroy(cs);
-  if (rc != YUMA_OK) {
-    if (g) (void)hipGraphDestroy(g);
-    return rc;  // run_impl's message stands
-  }
-  if (ec != hipSuccess || g == nullptr)
-    return fail(YUMA_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(ec));
-  hipGraphExec_t x = nullptr;
-  if (hipGraphInstantiate(&x, g, nullptr, nullptr, 0) != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    return fail(YUMA_EHIP, "hipGraphInstantiate failed");
-  }
-  *graph = new yuma_graph{g, x};
-  return YUMA_OK;
+  return graph_create_impl(graph, o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                           workspace_bytes, chunk_epochs);
+}
+
+int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
+                            int K, int V, int M, const float* W, const float* S, const int32_t* sched_dev,
+                            const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                            void* workspace, size_t workspace_bytes, int chunk_epochs,
+                            const yuma_run_options_t* opts) {
+  RunOpts o;
+  if (const int err = read_opts(opts, &o)) return err;
+  if (const int err = check_sched(sched_dev, K)) return err;
+  return graph_create_impl(graph, o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                           workspace_bytes, chunk_epochs, sched_dev, K);
 }
 
 int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,

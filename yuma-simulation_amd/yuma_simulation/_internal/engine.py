@@ -47,6 +47,10 @@ EXPORTED_SYMBOLS = (
     "yuma_run_ex",
     "yuma_run_opts",
     "yuma_hist_slots",
+    "yuma_workspace_bytes_sched",
+    "yuma_run_sched",
+    "yuma_sched_native",
+    "yuma_graph_create_sched",
     "yuma_epoch",
     "yuma_synth_weights",
     "yuma_shard_stage",
@@ -201,6 +205,18 @@ def load_library(path: str | None = None):
         lib.yuma_graph_create_ex.restype = i32
         lib.yuma_graph_create_opts.argtypes = lib.yuma_graph_create.argtypes + [vp]
         lib.yuma_graph_create_opts.restype = i32
+        # input schedules: E and K in place of E, the schedule after S
+        if hasattr(lib, "yuma_run_sched"):  # (A/B libraries of older sources lack them)
+            lib.yuma_workspace_bytes_sched.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+            lib.yuma_workspace_bytes_sched.restype = sz
+            lib.yuma_run_sched.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp, vp,
+                                           ctypes.POINTER(ctypes.c_float)]
+            lib.yuma_run_sched.restype = i32
+            lib.yuma_sched_native.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32]
+            lib.yuma_sched_native.restype = i32
+            lib.yuma_graph_create_sched.argtypes = [ctypes.POINTER(vp), i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
+                                                    vp, vp, vp, sz, i32, vp]
+            lib.yuma_graph_create_sched.restype = i32
         lib.yuma_graph_launch.argtypes = [vp, vp]
         lib.yuma_graph_launch.restype = i32
         lib.yuma_graph_nodes.argtypes = [vp]
@@ -499,6 +515,89 @@ def hist_bf16_native(variant: int, N: int, E: int, V: int, M: int, *, shared_inp
     return bool(load_library().yuma_hist_bf16_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
 
 
+_SCHED_REFUSED = _MATRIX_OUTPUTS + ("P", "T")  # what a run under an input schedule does not produce
+
+
+def sched_native(variant: int, N: int, E: int, K: int, V: int, M: int, want_hist: bool = False,
+                 want: tuple[str, ...] = (), *, shared_inputs: bool = False, w_u16: bool = False,
+                 hist_bf16: bool = False) -> bool:
+    """Whether `run(..., sched=)` with these arguments takes the schedule
+    natively (yuma_sched_native; needs the library, not a GPU): Yuma 3 / Yuma 4,
+    any V, M % 4 == 0, no shared inputs, none of Wn / Wc / Wb / B_inst / Tv /
+    P / T wanted; with w_u16 / hist_bf16, where u16_native / hist_bf16_native
+    hold too. Otherwise `run` expands W and S on the device and RunGraph
+    refuses."""
+    names = {"Dn", "C", "I", "B_final", *want}
+    if want_hist:
+        names.add("B_hist")
+    outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
+    flags = ((RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+             | (RUN_HIST_BF16 if hist_bf16 else 0))
+    return bool(load_library().yuma_sched_native(variant, N, E, K, V, M, ctypes.addressof(outs), flags))
+
+
+def _int_view(t: torch.Tensor) -> torch.Tensor:
+    """The elements of t as integers of the same width (bit patterns)."""
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+    if t.dtype == torch.uint16:
+        return t.view(torch.int16)
+    return t
+
+
+def _take_slices(t: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """t[idx] along dimension 0, bit for bit, for every dtype `run` takes."""
+    v = _int_view(t)
+    return v.index_select(0, idx.to(device=t.device, dtype=torch.long)).view(t.dtype)
+
+
+def dedup_slices(W: torch.Tensor, S: torch.Tensor):
+    """(Wk, Sk, sched) of per-epoch inputs W [E,N,V,M] and S [E,N,V]: the
+    distinct slices in order of first occurrence and the int32 schedule [E]
+    with W[t] == Wk[sched[t]] and S[t] == Sk[sched[t]] -- the inputs of
+    `run(..., sched=)`. Two epochs share a slice when both W[t] and S[t] are
+    equal bit for bit (integer views: -0.0 and +0.0 differ, NaN payloads
+    count). CPU or device tensors; W fp32 or uint16 (any dtype of 2, 4 or 8
+    bytes)."""
+    if W.dim() != 4 or S.dim() != 3 or tuple(S.shape) != tuple(W.shape[:3]):
+        raise ValueError(f"dedup_slices takes W [E,N,V,M] and S [E,N,V], not {tuple(W.shape)} and {tuple(S.shape)}")
+    E = W.shape[0]
+    if E == 0:
+        raise ValueError("dedup_slices needs at least one epoch")
+    S = S.to(W.device)
+    # classes of W rows and of S rows, then of the pairs
+    _, iw = torch.unique(_int_view(W.contiguous()).reshape(E, -1), dim=0, return_inverse=True)
+    _, i_s = torch.unique(_int_view(S.contiguous()).reshape(E, -1), dim=0, return_inverse=True)
+    _, inv = torch.unique(iw * (int(i_s.max()) + 1) + i_s, return_inverse=True)
+    K = int(inv.max()) + 1
+    t = torch.arange(E, device=inv.device)
+    first = torch.full((K,), E, dtype=torch.long, device=inv.device).scatter_reduce(0, inv, t, "amin")
+    order = torch.argsort(first)  # classes by first occurrence
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(K, device=inv.device)
+    reps = first[order]
+    return _take_slices(W, reps), _take_slices(S, reps), rank[inv].to(torch.int32)
+
+
+def _sched_host(sched, K: int) -> torch.Tensor:
+    """The schedule as a CPU int64 tensor, validated on the host: integers, one
+    dimension, at least one epoch, every entry in [0, K). ValueError otherwise."""
+    t = sched if isinstance(sched, torch.Tensor) else torch.as_tensor(np.asarray(sched))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"sched must hold integers, not {t.dtype}")
+    if t.dim() != 1 or t.numel() < 1:
+        raise ValueError(f"sched must be one-dimensional with one entry per epoch, not shape {tuple(t.shape)}")
+    h = t.detach().to(device="cpu", dtype=torch.int64)
+    lo, hi = int(h.min()), int(h.max())
+    if lo < 0 or hi >= K:
+        raise ValueError(f"sched entries must lie in [0, K={K}): found {lo if lo < 0 else hi}")
+    return h
+
+
+def workspace_bytes_sched(variant: int, N: int, E: int, K: int, V: int, M: int, full: bool) -> int:
+    return int(load_library().yuma_workspace_bytes_sched(variant, N, E, K, V, M, 1 if full else 0))
+
+
 def to_u16(W: torch.Tensor) -> torch.Tensor:
     """The on-chain max-upscale of float weights to 16 bits: per row (last
     dimension) round_half_even(w / rowmax * 65535), computed in float64; an
@@ -552,7 +651,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         workspace: torch.Tensor | None = None, out: dict | None = None,
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
-        hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None) -> RunResult:
+        hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -573,17 +672,39 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     (YUMA_RUN_HIST_BF16, extra["hist_path"] == "bf16"); elsewhere the run
     writes an fp32 history and converts it on the device (extra["hist_path"] ==
     "f32"; a captured run raises EngineError instead). A caller's out["B_hist"]
-    must be bfloat16. For reading, not for resuming: resume from B_final."""
+    must be bfloat16. For reading, not for resuming: resume from B_final.
+    sched: an input schedule, a sequence or integer tensor of length E. W is
+    then [K,N,V,M] and S [K,N,V], the stored slices, and epoch t reads slice
+    sched[t] (dedup_slices builds the three from per-epoch inputs). Every
+    output, hist_epochs included, is that of the run on W[sched], S[sched],
+    bit for bit. The schedule is validated on the host (ValueError). Where
+    sched_native holds (and the buffers have the vector form's alignment) the
+    engine stores K slices and runs phase 1 once per stored slice
+    (yuma_run_sched, extra["sched_path"] == "native"; extra["sched"] is the
+    int32 device tensor a captured run re-reads at every replay); elsewhere,
+    and under single_call, the inputs are expanded on the device and the dense
+    path runs (extra["sched_path"] == "expanded"; a captured run raises
+    EngineError instead)."""
     if hist_dtype not in (None, torch.float32, torch.bfloat16):
         raise ValueError(f"hist_dtype={hist_dtype} must be None, torch.float32 or torch.bfloat16")
     h_bf16 = hist_dtype == torch.bfloat16
     if h_bf16 and single_call:
         raise ValueError("single_call (yuma_epoch) writes an fp32 history: no hist_dtype=torch.bfloat16")
     E, Nw, V, M = W.shape
+    sched_host = None
+    if sched is not None:  # validated before anything touches a GPU
+        K = E
+        sched_host = _sched_host(sched, K)
+        E = sched_host.numel()
+        for name, t in (out or {}).items():  # a caller's per-epoch outputs follow the schedule's length
+            if t is not None and name not in ("B_hist", "B_final") and t.shape[0] != E:
+                raise ValueError(f"out[{name!r}] holds {t.shape[0]} epochs, the schedule {E}")
+        if S.shape != (K, Nw, V):
+            raise ValueError(f"S shape {tuple(S.shape)} is not [K={K}, N={Nw}, V={V}] of W {tuple(W.shape)}")
     check_limits(V, M)
     dev = device()
     lib = load_library()
-    if S.shape != (E, Nw, V):
+    if sched is None and S.shape != (E, Nw, V):
         raise ValueError(f"S shape {tuple(S.shape)} does not match W {tuple(W.shape)}")
     n_scen = len(params) if shared_inputs else Nw
     h_epochs = hist_epochs(E, hist_stride, hist_first)
@@ -667,14 +788,6 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         if o["B_hist"].dtype != torch.float32:  # the run's fp32 history, converted below
             o["B_hist"] = torch.empty((len(h_epochs), N, V, M), dtype=torch.float32, device=dev)
     full = o.get("Tv") is not None
-    nbytes = workspace_bytes(variant, N, E, V, M, full)
-    if workspace is None or workspace.numel() < nbytes:
-        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    outs = YumaOutputsC(**{k: _ptr(o.get(k)) for k in OUTPUT_FIELDS})
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    args = (variant, prm.data_ptr(), N, E, V, M, W.data_ptr(), S.data_ptr(),
-            _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
-            workspace.data_ptr(), workspace.numel(), int(chunk_epochs), stream)
     if w_u16:
         # the fp32 matrices of the vector paths: a view at an odd offset sends
         # the fp32 run to its scalar loads, which the uint16 kernels lack
@@ -682,8 +795,52 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         if any(t is not None and t.data_ptr() % 16 for t in mats):
             w_u16 = False
             W = _as_dev(W, dev)
-            args = args[:6] + (W.data_ptr(),) + args[7:]
-    if strided or hist_native:  # yuma_run_opts / yuma_graph_create_opts: the history options, with the run's flags
+    sched_dev = None
+    if sched is not None:
+        names = tuple(k for k, v in o.items() if v is not None and k != "B_hist")
+        native = (not single_call
+                  and sched_native(variant, N, E, K, V, M, o.get("B_hist") is not None, names,
+                                   shared_inputs=shared_inputs))
+        if native:  # the vector form, as the engine tests it
+            mats = [B_init, Wprev_init, o.get("B_final")] + ([] if hist_native else [o.get("B_hist")])
+            native = not (W.data_ptr() % (8 if w_u16 else 16) or any(t is not None and t.data_ptr() % 16 for t in mats))
+        if native:
+            if (isinstance(sched, torch.Tensor) and sched.device == dev and sched.dtype == torch.int32
+                    and sched.is_contiguous()):
+                sched_dev = sched  # the caller's tensor: a captured run follows its in-place updates
+            else:
+                sched_dev = sched_host.to(device=dev, dtype=torch.int32)
+        else:
+            if capture is not None:
+                raise EngineError("a captured run cannot expand its inputs: sched= needs "
+                                  "sched_native(variant, N, E, K, V, M, ...) and vector-aligned buffers")
+            W, S = _take_slices(W, sched_host.to(dev)), _take_slices(S, sched_host.to(dev))
+    if sched_dev is not None:
+        nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
+    else:
+        nbytes = workspace_bytes(variant, N, E, V, M, full)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    outs = YumaOutputsC(**{k: _ptr(o.get(k)) for k in OUTPUT_FIELDS})
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    args = (variant, prm.data_ptr(), N, E, V, M, W.data_ptr(), S.data_ptr(),
+            _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
+            workspace.data_ptr(), workspace.numel(), int(chunk_epochs), stream)
+    if sched_dev is not None:  # yuma_run_sched / yuma_graph_create_sched, with every option of the run
+        opts = YumaRunOptionsC(flags=(RUN_W_U16 if w_u16 else 0) | (RUN_HIST_BF16 if hist_native else 0),
+                               hist_stride=min(int(hist_stride), E), hist_first=h_epochs[0] if h_epochs else E)
+        sargs = args[:4] + (K,) + args[4:8] + (sched_dev.data_ptr(),) + args[8:14] + (ctypes.addressof(opts),)
+        if capture is not None:
+            h = ctypes.c_void_p()
+            torch.cuda.synchronize(dev)
+            _check(lib.yuma_graph_create_sched(ctypes.byref(h), *sargs), "yuma_graph_create_sched")
+            capture.append(h)
+        else:
+            buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
+            _check(lib.yuma_run_sched(*sargs, stream, buf), "yuma_run_sched")
+            if phase_ms is not None:
+                phase_ms[:] = list(buf)
+    elif strided or hist_native:  # yuma_run_opts / yuma_graph_create_opts: the history options, with the run's flags
         opts = YumaRunOptionsC(flags=(RUN_W_U16 if w_u16 else 0) | (RUN_SHARED_INPUTS if shared_inputs else 0)
                                | (RUN_HIST_BF16 if hist_native else 0),
                                # (a stride of E or more stores one epoch at the most: int32 either way)
@@ -741,6 +898,9 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
     keep["w_path"] = "u16" if w_u16 else "f32"  # how W was read: natively as uint16, or as fp32
     keep["hist_path"] = "bf16" if hist_native else "f32"  # how the scan wrote the history
+    if sched is not None:  # how the schedule was taken: by the engine, or expanded to a slice per epoch
+        keep["sched_path"] = "native" if sched_dev is not None else "expanded"
+        keep["sched"] = sched_dev
     hist = o.get("B_hist")
     if h_bf16 and hist is not None and not hist_native:  # the fp32 history, rounded to nearest even
         hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)

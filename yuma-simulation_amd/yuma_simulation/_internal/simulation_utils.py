@@ -92,7 +92,8 @@ def _reward_key(config: YumaConfig) -> tuple:
 
 
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
-                    want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None):
+                    want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None,
+                    dedup_inputs: bool = False):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
@@ -104,7 +105,12 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     then bfloat16, each the fp32 bond state rounded to nearest even (engine.run's
     hist_dtype: written as 16 bits by the bond scan where the engine can, half
     the history's device memory and half the bytes of its copy to the host).
-    For reading and charting; dividends and incentives are unchanged."""
+    For reading and charting; dividends and incentives are unchanged.
+    dedup_inputs: each group's stacked inputs go to the engine as their
+    distinct (W, S) slices and a schedule (engine.dedup_slices, engine.run's
+    sched): the cases hold a few matrices for tens of epochs each, so the
+    engine stores and analyses each distinct slice once. Every returned
+    dividend, bond and incentive is bit-identical to the default."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
     if bonds_dtype not in (None, torch.float32, torch.bfloat16):
@@ -114,7 +120,7 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     # heap several times while they are built; they hold no cycles
     with _no_cyclic_gc():
         return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every),
-                                bonds_dtype=bonds_dtype)
+                                bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs))
 
 
 @contextmanager
@@ -171,7 +177,7 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
-                     totals: bool = False, bonds_every: int = 1, bonds_dtype=None):
+                     totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -211,8 +217,11 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
                     local[lk] = rec
             params.append(rec)
         W, S, S_host = _group_inputs([packed[k] for k in idx], E * V * M * len(idx))
+        sched = None
+        if dedup_inputs:  # the group's distinct joint slices and the schedule over them
+            W, S, sched = engine.dedup_slices(W, S)
         launched.append((E, V, idx, S_host, engine.run(variant, params, W, S, want_hist=want_bonds,
-                                                              hist_stride=bonds_every,
+                                                              hist_stride=bonds_every, sched=sched,
                                                               hist_dtype=bonds_dtype if want_bonds else None)))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
