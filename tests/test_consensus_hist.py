@@ -10,7 +10,11 @@ it against the oracle's plain bisection (oracle.yuma_oracle.consensus) on
 exact-stake inputs: random and integer weights, zero rows / columns, ties on
 grid points, NaN / ±inf / negative weights, every κ and precision setting the
 GPU tests use. The GPU path itself is compared with the bisection bitwise in
-tests/test_gpu_parity.py::test_consensus_histogram_finish_equals_bisection.
+tests/test_gpu_parity.py::test_consensus_histogram_finish_equals_bisection,
+and every kernel form of the consensus pass (k_consensus_p's own finish, the
+block-wide and streamed forms, sweeps, uint16 weights, shard stages) runs on
+adversarial exact-stake columns against a big-integer reference in
+tests/test_gpu_consensus_forms.py (inputs: tests/consensus_cases.py).
 """
 
 import zlib

@@ -592,6 +592,8 @@ def test_consensus_histogram_finish_equals_bisection(V, M, kind):
         torch.cuda.synchronize()
         assert torch.equal(a.C, b.C), tag
         assert torch.equal(bits(a.B_hist), bits(b.B_hist)) and torch.equal(bits(a.Dn), bits(b.Dn)), tag
-        if kind != "nan_inf":
+        # (nan_inf too: the histogram and the bisection share their bracket, so
+        # agreeing with each other is not agreeing with the reference)
+        with np.errstate(invalid="ignore", over="ignore"):
             ref = orc.run("Yuma 3 (Rhef)", W[:, 0], S[:, 0], cfg)
-            np.testing.assert_array_equal(a.C[:, 0].cpu().numpy(), ref["C"], err_msg=tag)
+        np.testing.assert_array_equal(a.C[:, 0].cpu().numpy(), ref["C"], err_msg=tag)
