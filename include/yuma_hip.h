@@ -310,7 +310,12 @@ int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma
  * outputs. Capture happens on an internal stream; `stream` orders the capture
  * after the caller's prior work only through the caller's own sync, so call
  * it with inputs already resident. Replaces the per-epoch Python loop of
- * run_simulation (simulation_utils.py:52-110) for repeated runs.            */
+ * run_simulation (simulation_utils.py:52-110) for repeated runs.
+ * Every yuma_graph_create* reads its flags / options / schedule as its run
+ * entry point does, then checks `graph` (NULL: YUMA_EINVAL; else *graph = NULL
+ * until the graph exists), then validates the rest exactly as that run entry
+ * point does, in its order, before the capture opens: the same code and
+ * yuma_last_error text, and nothing is refused inside an open capture.      */
 typedef struct yuma_graph* yuma_graph_t;
 int yuma_graph_create(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
                       int E, int V, int M, const float* W, const float* S,

@@ -2,7 +2,8 @@
 metadata and code bytes; no GPU needed): code size, VGPR / SGPR counts, spills,
 scratch, LDS and kernel-argument size of every k_bonds* / k_rust_big_* kernel
 that both hold, and whether its machine code is byte-identical.
-    python tools/kcompare.py parent/libyuma_hip.so [this/libyuma_hip.so] [-v]
+    python tools/kcompare.py parent/libyuma_hip.so [this/libyuma_hip.so] [-v] [--all]
+--all compares every kernel of the two code objects, not only the bond scans.
 k_bonds_elem's trailing history element type (HT = float, the default) is
 dropped from a name before the two sides are matched, so that a library built
 before that parameter existed pairs with one built after."""
@@ -20,8 +21,9 @@ FIELDS = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "p
 TAIL = "EEvNS_8BondArgsE"
 
 
-def kernels(lib):
-    """mangled name -> (code bytes, sha1 of the code, the metadata FIELDS)"""
+def kernels(lib, every=False):
+    """mangled name -> (code bytes, sha1 of the code, the metadata FIELDS) of
+    the k_bonds* / k_rust_big_* kernels, or (every) of all kernels"""
     with tempfile.TemporaryDirectory() as t:
         subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={t}/fb", lib], check=True)
         subprocess.run([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={t}/fb",
@@ -40,7 +42,7 @@ def kernels(lib):
     out = {}
     for e in re.split(r"\n\s*- \.agpr_count", notes):
         m = re.search(r"\.name:\s+(\S+)", e)
-        if not m or not re.search(r"k_bonds|k_rust_big", m.group(1)):
+        if not m or not (every or re.search(r"k_bonds|k_rust_big", m.group(1))):
             continue
         meta = tuple((re.search(r"\." + k + r":\s+(\d+)", e) or [None, "-"])[1] for k in FIELDS)
         out[m.group(1)] = code.get(m.group(1), (None, None)) + (meta,)
@@ -58,15 +60,16 @@ def key(name):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "-v"]
-    a = kernels(args[0])
-    b = kernels(args[1] if len(args) > 1 else os.path.join(ROOT, "yuma-simulation_amd", "lib", "libyuma_hip.so"))
+    every = "--all" in sys.argv
+    args = [a for a in sys.argv[1:] if a not in ("-v", "--all")]
+    a = kernels(args[0], every)
+    b = kernels(args[1] if len(args) > 1 else os.path.join(ROOT, "yuma-simulation_amd", "lib", "libyuma_hip.so"), every)
     A = {key(k): v for k, v in a.items()}
     B = {key(k): v for k, v in b.items()}
     both = sorted(set(A) & set(B))
     meta = [k for k in both if (A[k][0], A[k][2]) != (B[k][0], B[k][2])]
     code = [k for k in both if A[k][1] != B[k][1]]
-    print(f"bond-scan kernels: {len(A)} in the first library, {len(B)} in the second, {len(both)} in both")
+    print(f"{'all' if every else 'bond-scan'} kernels: {len(A)} in the first library, {len(B)} in the second, {len(both)} in both")
     print(f"  code size / registers / spills / scratch / LDS / kernarg differ: {len(meta)}")
     print(f"  machine code differs: {len(code)}")
     print(f"  only in the first: {len(set(A) - set(B))}")

@@ -5599,8 +5599,8 @@ int launch_cn_rows(hipStream_t st, yk::BondArgs& A, int* ptiles) {
   if (V <= 512) return launch_cn<VARIANT, 4>(st, A, ptiles);
   return launch_cn<VARIANT, 8>(st, A, ptiles);
 }
-template <int VARIANT, bool VEC, typename WT = float>
-int launch_bonds_elem(hipStream_t st, yk::BondArgs& A);
+template <int VARIANT, bool VEC, typename WT = float, bool SC = false>
+int launch_bonds_elem(hipStream_t st, yk::BondArgs& A, const int32_t* sched = nullptr, int nk = 0);
 template <int VARIANT, bool VEC>
 int launch_bonds_colnorm(RowCfg rc, hipStream_t st, yk::BondArgs& A, int* ptiles) {
   if (A.V > yk::kRegRows) {  // no workgroup holds a column: streaming forms
@@ -5713,12 +5713,16 @@ int launch_elem_shape(hipStream_t st, yk::BondArgs& A, const int32_t* sched = nu
 // the shared-input sweep scan)
 // A strided history (hist_strided) runs the dense history's shape at every
 // stride, in that shape's HS instantiation ("Strided bond history").
-// A bfloat16 history (BondArgs::hbf16; run_impl admits it for Yuma 3 / Yuma 4
+// A bfloat16 history (BondArgs::hbf16; run_plan admits it for Yuma 3 / Yuma 4
 // in vector form without shared inputs, where a history is written from the
 // wide or the 64-miner-tile shape only) runs the same two shapes with
 // HT = __bf16 ("bfloat16 bond history").
-template <int VARIANT, bool VEC, typename WT>
-int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
+// SC: the scan under an input schedule of nk stored slices (yuma_sched_native:
+// Yuma 3 / Yuma 4, vector form, no shared inputs, k_rowsum's reciprocals at
+// hand), in the SC instantiation of the shape chosen here. That fixes three
+// choices: no sweep scan, the screened reciprocal, a non-temporal tile history.
+template <int VARIANT, bool VEC, typename WT, bool SC>
+int launch_bonds_elem(hipStream_t st, yk::BondArgs& A, const int32_t* sched, int nk) {
   const bool hist = A.B_hist != nullptr;
   const bool hs = hist && yk::hist_strided(A);
   if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3) {
@@ -5727,8 +5731,9 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
         constexpr bool kHs = decltype(HS)::value;
         if (A.M >= 1024)
           return launch_elem_shape<WT, VARIANT, 2, true, kWideP, true, true, 512, 1024, yk::DP_VQ, false, kHs,
-                                   __bf16>(st, A);
-        return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, __bf16>(st, A);
+                                   __bf16, SC>(st, A, sched, nk);
+        return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, __bf16, SC>(
+            st, A, sched, nk);
       });
     }
   }
@@ -5739,12 +5744,12 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
         constexpr bool kRq = kElemRq(VARIANT, true) && decltype(RQ)::value;
         return with_bool(hs, [&](auto HS) {
           return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, kRq,
-                                   decltype(HS)::value>(st, A);
+                                   decltype(HS)::value, float, SC>(st, A, sched, nk);
         });
       });
     }
   }
-  if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float>) {
+  if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float> && !SC) {
     if (A.wsh && A.N >= 2 && A.rq4 != nullptr) {  // a sweep over one input trajectory
       constexpr int K = kScanGroup, R = 2;
       A.rowblocks = (A.V + 16 * R - 1) / (16 * R);
@@ -5772,54 +5777,29 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A) {
         return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, false, true>(st, A);
       }
     }
-    return with_bool(kRqOk && A.rq4 != nullptr, [&](auto RQ) {
+    auto go = [&](auto RQ) {
       constexpr bool kRq = kRqOk && decltype(RQ)::value;
       if (blocks_r2 >= 4096)
-        return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, kRq>(st, A);
-      return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, kRq>(st, A);
-    });
+        return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, kRq, false, float,
+                                 SC>(st, A, sched, nk);
+      return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, kRq, false, float, SC>(
+          st, A, sched, nk);
+    };
+    if constexpr (SC)
+      return go(std::true_type{});
+    else
+      return with_bool(kRqOk && A.rq4 != nullptr, go);
   }
-  if (hs) return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, true, 256, 64, yk::DP_TV, false, true>(st, A);
-  return with_bool(hist, [&](auto HIST) {  // the history goes out with non-temporal stores
-    return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, decltype(HIST)::value, 256, 64, yk::DP_TV>(st, A);
-  });
-}
-
-// The scan under an input schedule (yuma_sched_native: Yuma 3 / Yuma 4, vector
-// form, no shared inputs, k_rowsum's reciprocals at hand): launch_bonds_elem's
-// choice of shape for such a run, decision for decision, in the SC
-// instantiations -- the bfloat16 and fp32 history from the wide or the
-// 64-miner-tile shape (dense or strided), the history-less forms with the
-// screened reciprocal.
-template <int VARIANT, typename WT>
-int launch_bonds_elem_sc(hipStream_t st, yk::BondArgs& A, const int32_t* sched, int K) {
-  const bool hist = A.B_hist != nullptr;
-  const bool hs = hist && yk::hist_strided(A);
-  if (A.hbf16)
-    return with_bool(hs, [&](auto HS) {
-      constexpr bool kHs = decltype(HS)::value;
-      if (A.M >= 1024)
-        return launch_elem_shape<WT, VARIANT, 2, true, kWideP, true, true, 512, 1024, yk::DP_VQ, false, kHs, __bf16,
-                                 true>(st, A, sched, K);
-      return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, __bf16, true>(
-          st, A, sched, K);
-    });
-  if (!hist) {
-    const long long blocks_r2 = (long long)A.N * ((A.V + 7) / 8) * ((A.M + 255) / 256);
-    if (blocks_r2 >= 4096)
-      return launch_elem_shape<WT, VARIANT, 2, true, kNoHistP2, true, false, 256, 256, yk::DP_QTE, true, false, float,
-                               true>(st, A, sched, K);
-    return launch_elem_shape<WT, VARIANT, 1, true, 4, true, false, 256, 256, yk::DP_QTE, true, false, float, true>(
-        st, A, sched, K);
-  }
-  return with_bool(hs, [&](auto HS) {
-    constexpr bool kHs = decltype(HS)::value;
-    if (A.M >= 1024)
-      return launch_elem_shape<WT, VARIANT, 2, true, kWideP, true, true, 512, 1024, yk::DP_VQ, false, kHs, float,
-                               true>(st, A, sched, K);
-    return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, float, true>(
-        st, A, sched, K);
-  });
+  // the 64-miner tiles; the history goes out with non-temporal stores
+  auto tile = [&](auto NT, auto HS) {
+    return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, decltype(NT)::value, 256, 64, yk::DP_TV, false,
+                             decltype(HS)::value, float, SC>(st, A, sched, nk);
+  };
+  if (hs) return tile(std::true_type{}, std::true_type{});
+  if constexpr (SC)  // (without a history a schedule run took the forms above)
+    return tile(std::true_type{}, std::false_type{});
+  else
+    return with_bool(hist, [&](auto HIST) { return tile(HIST, std::false_type{}); });
 }
 
 // Launch the bond scan for A.N scenarios over epochs [A.t0, A.t1); returns
@@ -5902,7 +5882,7 @@ bool sched_native(int variant, int N, int E, int K, int V, int M, const yuma_out
   return true;
 }
 
-// What run_impl and shard_stage_impl decide alike.
+// What run_plan and shard_stage_impl decide alike.
 int check_sizes(int variant, int N, int E, int V, int M) {
   if (variant < 0 || variant > 4) return fail(YUMA_EINVAL, "unknown variant %d", variant);
   if (N < 1 || E < 1 || V < 1 || M < 1)
@@ -5916,10 +5896,9 @@ int check_sizes(int variant, int N, int E, int V, int M) {
 // Vector form: a lane's 4 columns are one vector load (16 bytes of fp32, 8 of
 // uint16) of W and of every fp32 matrix read or written
 // (8 bytes of a bfloat16 history: hist_bf16)
-template <typename WT>
-bool vector_form(int M, const WT* W, const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
-                 bool hist_bf16 = false) {
-  if ((M % 4) != 0 || ((uintptr_t)W & (4 * sizeof(WT) - 1)) != 0) return false;
+bool vector_form(int M, const void* W, const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                 bool hist_bf16 = false, size_t wsize = sizeof(float)) {
+  if ((M % 4) != 0 || ((uintptr_t)W & (4 * wsize - 1)) != 0) return false;
   const float* mats[] = {B_init, Wprev_init, out->Wn, out->Wc, out->Wb, out->B_inst,
                          hist_bf16 ? nullptr : out->B_hist, out->B_final};
   for (const float* p : mats)
@@ -6004,41 +5983,58 @@ void launch_finalize(hipStream_t st, long long ns, const float* dsrc, const Work
               out->Tv, dpl, tiles);
 }
 
-// WT: the element type of W, float or (YUMA_RUN_W_U16) uint16_t. Element w of
-// a uint16 W is the weight (float)w; slices and rows are indexed in elements.
-template <typename WT>
-int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, const WT* W,
-             const float* S, const float* B_init, const float* Wprev_init,
-             const yuma_outputs_t* out, void* workspace, size_t ws_bytes, int chunk,
-             void* stream, float* phase_ms = nullptr, int wsh = 0, int hist_stride = 1, int hist_first = 0,
-             int hist_bf16 = 0, const int32_t* sched = nullptr, int K = 0) {
-  // sched (yuma_run_sched): W is [K][N][V][M], S [K][N][V], and epoch t reads
-  // stored slice sched[t] ([E], device memory). Phase 1 then runs once per
-  // stored slice into a staging set carved behind the E-epoch workspace, and
-  // k_sched_expand gathers its per-slice vectors into the per-epoch arrays;
-  // the bond scan, k_finalize and the output copies run per epoch as ever.
-  constexpr bool U16 = std::is_same_v<WT, uint16_t>;
-  static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
+// One run as its entry point received it, the yuma_run_options_t resolved
+// (read_opts): every run and graph entry point fills one for run_direct / graph_create_impl.
+struct RunReq {
+  int variant;
+  const yuma_params_t* prm;
+  int N, E, V, M;
+  const void* W;  // fp32, or uint16 under w_u16: element w is the weight (float)w
+  const float *S, *B_init, *Wprev_init;
+  const yuma_outputs_t* out;
+  void* workspace;
+  size_t ws_bytes;
+  int chunk;
+  void* stream;
+  float* phase_ms;  // [YUMA_NUM_PHASES] of a profiled run, or nullptr
+  int wsh = 0, w_u16 = 0, hist_bf16 = 0;  // YUMA_RUN_SHARED_INPUTS / _W_U16 / _HIST_BF16
+  int hist_stride = 1, hist_first = 0;
+  // yuma_run_sched: W is [K][N][V][M], S [K][N][V]; epoch t reads stored slice sched[t] ([E], device memory)
+  const int32_t* sched = nullptr;
+  int K = 0;
+};
+
+// What run_plan resolves for run_impl: the carved workspace (wk: the staging
+// set of an input schedule's K stored slices), the vector form, the shapes.
+struct RunPlan {
+  Workspace ws, wk;
+  bool vec;
+  int tiles;
+  RowCfg rc;
+};
+
+// Validate: every refusal of a run, in the order the entry points document,
+// without a HIP call -- so that a capture is refused before it opens
+// (graph_create_impl) by the code and text the direct run returns.
+int run_plan(const RunReq& q, RunPlan* p) {
+  const int variant = q.variant, N = q.N, E = q.E, V = q.V, M = q.M, K = q.K, wsh = q.wsh;
+  const yuma_outputs_t* out = q.out;
   if (const int err = check_sizes(variant, N, E, V, M)) return err;
   if ((M + yk::kTileM - 1) / yk::kTileM > yk::kMaxTiles) return fail(YUMA_EINVAL, "M too large");
-  if (!prm || !W || !S || !out || !workspace)
-    return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
-  if (sched != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
+  if (!q.prm || !q.W || !q.S || !out || !q.workspace) return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
+  if (q.sched != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
   const int full = out->Tv != nullptr;
   // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
   // params live in device memory, so the Python marshaller enforces it.
-  Workspace ws = carve((char*)workspace, variant, N, E, V, M, full);
-  Workspace wk{};  // the staging set of the K stored slices
-  if (sched != nullptr) wk = carve((char*)workspace + ws.bytes, variant, N, K, V, M, 0, true);
-  if (ws.bytes + wk.bytes > ws_bytes)
+  p->ws = carve((char*)q.workspace, variant, N, E, V, M, full);
+  p->wk = q.sched ? carve((char*)q.workspace + p->ws.bytes, variant, N, K, V, M, 0, true) : Workspace{};
+  if (p->ws.bytes + p->wk.bytes > q.ws_bytes)
     return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)",
-                ws_bytes, ws.bytes + wk.bytes, full);
-  hipStream_t st = (hipStream_t)stream;
-  const int tiles = (M + yk::kTileM - 1) / yk::kTileM;
-  const RowCfg rc = row_cfg(V);
-
-  const bool vec = vector_form(M, W, B_init, Wprev_init, out, hist_bf16 != 0);
-  if (sched != nullptr) {  // before the first launch (the uint16 / bfloat16 tests of their own follow)
+                q.ws_bytes, p->ws.bytes + p->wk.bytes, full);
+  p->tiles = (M + yk::kTileM - 1) / yk::kTileM;
+  p->rc = row_cfg(V);
+  const bool vec = p->vec = vector_form(M, q.W, q.B_init, q.Wprev_init, out, q.hist_bf16 != 0, q.w_u16 ? 2 : 4);
+  if (q.sched != nullptr) {  // (the uint16 / bfloat16 tests of their own follow)
     const int f = wsh ? YUMA_RUN_SHARED_INPUTS : 0;
     if (!sched_native(variant, N, E, K, V, M, out, f))
       return fail(YUMA_EUNSUPPORTED,
@@ -6050,7 +6046,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
                   "an input schedule (yuma_sched_native) needs the vector form: W vector-aligned and the fp32 "
                   "matrices 16-byte aligned");
   }
-  if (hist_bf16) {  // before the first launch
+  if (q.hist_bf16) {
     if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
     if (!hist_bf16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
       return fail(YUMA_EUNSUPPORTED,
@@ -6062,7 +6058,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
                   "YUMA_RUN_HIST_BF16 needs B_hist 8-byte aligned, W vector-aligned and the fp32 matrices "
                   "16-byte aligned");
   }
-  if constexpr (U16) {  // before the first launch
+  if (q.w_u16) {
     if (!u16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
       return fail(YUMA_EUNSUPPORTED,
                   "YUMA_RUN_W_U16 is not native for variant=%d V=%d M=%d shared=%d or the requested "
@@ -6072,8 +6068,33 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
       return fail(YUMA_EUNSUPPORTED,
                   "YUMA_RUN_W_U16 needs W 8-byte aligned and the fp32 matrices 16-byte aligned");
   }
+  return YUMA_OK;
+}
 
-  // VEC as a template argument; uint16 runs are vector form only (checked above)
+// Enqueue the run that run_plan admitted, on q.stream. WT: the element type
+// of W, float or (YUMA_RUN_W_U16) uint16_t; slices and rows are indexed in elements.
+// Under an input schedule phase 1 runs once per stored slice into the staging
+// set carved behind the E-epoch workspace, and k_sched_expand gathers its
+// per-slice vectors into the per-epoch arrays; the bond scan, k_finalize and
+// the output copies run per epoch as ever.
+template <typename WT>
+int run_impl(const RunReq& q, const RunPlan& plan) {
+  constexpr bool U16 = std::is_same_v<WT, uint16_t>;
+  static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
+  const int variant = q.variant, N = q.N, E = q.E, V = q.V, M = q.M, K = q.K, wsh = q.wsh;
+  const int hist_stride = q.hist_stride, hist_first = q.hist_first, tiles = plan.tiles, chunk0 = q.chunk;
+  const RowCfg rc = plan.rc;
+  const yuma_params_t* prm = q.prm;
+  const WT* W = static_cast<const WT*>(q.W);
+  const float *S = q.S, *B_init = q.B_init, *Wprev_init = q.Wprev_init;
+  const yuma_outputs_t* out = q.out;
+  const int32_t* sched = q.sched;
+  float* phase_ms = q.phase_ms;
+  const Workspace &ws = plan.ws, &wk = plan.wk;
+  const bool vec = plan.vec;
+  hipStream_t st = (hipStream_t)q.stream;
+
+  // VEC as a template argument; uint16 runs are vector form only (run_plan)
   auto with_vec = [&](auto f) {
     if constexpr (U16)
       return f(std::true_type{});
@@ -6084,8 +6105,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
   const Bufs buf = pick_bufs(out, ws);
 
   // one chunk by default: phase 1 of every epoch, then one bond scan
-  if (chunk <= 0 || chunk > E) chunk = E;
-
+  const int chunk = (chunk0 <= 0 || chunk0 > E) ? E : chunk0;
 
   // Shared inputs: scenarios with the same consensus parameters take one
   // representative's consensus, quantisation input and (streaming) rank
@@ -6220,7 +6240,7 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
     A.t0 = c0;
     A.t1 = c1;
     A.wsh = wsh;
-    A.hbf16 = hist_bf16;
+    A.hbf16 = q.hist_bf16;
     {
       // the history countdown of this chunk (BondArgs::hnext): epochs count
       // from the run's epoch 0, so the slot follows the absolute epoch
@@ -6233,9 +6253,9 @@ int run_impl(int variant, const yuma_params_t* prm, int N, int E, int V, int M, 
     tm.mark(YUMA_PHASE_BONDS);
     int ptiles = tiles;
     int dpl;
-    if (sched != nullptr)  // (Yuma 3 / Yuma 4 in vector form: checked above)
-      dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem_sc<YUMA_VARIANT_YUMA3, WT>(st, A, sched, K)
-                                          : launch_bonds_elem_sc<YUMA_VARIANT_YUMA4, WT>(st, A, sched, K);
+    if (sched != nullptr)  // (Yuma 3 / Yuma 4 in vector form: run_plan)
+      dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem<YUMA_VARIANT_YUMA3, true, WT, true>(st, A, sched, K)
+                                          : launch_bonds_elem<YUMA_VARIANT_YUMA4, true, WT, true>(st, A, sched, K);
     else if constexpr (U16)
       dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem<YUMA_VARIANT_YUMA3, true, WT>(st, A)
                                           : launch_bonds_elem<YUMA_VARIANT_YUMA4, true, WT>(st, A);
@@ -6396,12 +6416,8 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
 constexpr int kRunFlags = YUMA_RUN_SHARED_INPUTS | YUMA_RUN_W_U16 | YUMA_RUN_HIST_BF16;
 
 namespace {
-// yuma_run_options_t checked and resolved: NULL is every default; stride 0 is 1.
-struct RunOpts {
-  int flags, stride, first;
-};
-int read_opts(const yuma_run_options_t* o, RunOpts* r) {
-  *r = RunOpts{0, 1, 0};
+// yuma_run_options_t checked and resolved into the request: NULL keeps RunReq's defaults; stride 0 is 1.
+int read_opts(const yuma_run_options_t* o, RunReq* q) {
   if (o == nullptr) return YUMA_OK;
   if (o->flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", o->flags);
   if (o->hist_stride < 0 || o->hist_first < 0)
@@ -6409,31 +6425,28 @@ int read_opts(const yuma_run_options_t* o, RunOpts* r) {
                 o->hist_first);
   for (int w : o->reserved)
     if (w != 0) return fail(YUMA_EINVAL, "yuma_run_options_t.reserved must be 0");
-  *r = RunOpts{o->flags, o->hist_stride == 0 ? 1 : o->hist_stride, o->hist_first};
+  q->wsh = (o->flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
+  q->w_u16 = (o->flags & YUMA_RUN_W_U16) ? 1 : 0;
+  q->hist_bf16 = (o->flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
+  q->hist_stride = o->hist_stride == 0 ? 1 : o->hist_stride;
+  q->hist_first = o->hist_first;
   return YUMA_OK;
 }
 
-// run_impl for resolved options, in the weight type the flags name. sched:
-// the input schedule of yuma_run_sched (K stored slices), or NULL.
-int run_with(const RunOpts& o, int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
-             const float* W, const float* S, const float* B_init, const float* Wprev_init,
-             const yuma_outputs_t* out, void* workspace, size_t workspace_bytes, int chunk_epochs, void* stream,
-             float* phase_ms, const int32_t* sched = nullptr, int K = 0) {
-  const int wsh = (o.flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
-  const int hbf = (o.flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
-  if (o.flags & YUMA_RUN_W_U16)
-    return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
-                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride,
-                    o.first, hbf, sched, K);
-  return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, o.stride, o.first, hbf, sched, K);
-}
-
-// What yuma_run_sched and yuma_graph_create_sched refuse alike, before any launch.
-int check_sched(const int32_t* sched_dev, int K) {
+// What yuma_run_sched and yuma_graph_create_sched refuse alike, first; then the schedule is the request's.
+int read_sched(const int32_t* sched_dev, int K, RunReq* q) {
   if (K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
   if (sched_dev == nullptr) return fail(YUMA_EINVAL, "the schedule pointer is NULL");
+  q->sched = sched_dev;
+  q->K = K;
   return YUMA_OK;
+}
+
+// A direct run: validate, then enqueue on the caller's stream, in the weight type the request names.
+int run_direct(const RunReq& q) {
+  RunPlan p;
+  if (const int err = run_plan(q, &p)) return err;
+  return q.w_u16 ? run_impl<uint16_t>(q, p) : run_impl<float>(q, p);
 }
 }  // namespace
 
@@ -6443,26 +6456,13 @@ struct yuma_graph {
 };
 
 namespace {
-// The capture behind every yuma_graph_create*: run_with on a capture stream.
-int graph_create_impl(yuma_graph_t* graph, const RunOpts& o, int variant, const yuma_params_t* params_dev, int N,
-                      int E, int V, int M, const float* W, const float* S, const float* B_init,
-                      const float* Wprev_init, const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
-                      int chunk_epochs, const int32_t* sched = nullptr, int K = 0) {
-  const int flags = o.flags;
+// The capture behind every yuma_graph_create*: the request validated as a
+// direct run validates it, then enqueued on a capture stream of its own.
+int graph_create_impl(yuma_graph_t* graph, RunReq q) {
   if (graph == nullptr) return fail(YUMA_EINVAL, "graph handle pointer is NULL");
   *graph = nullptr;
-  // refused before the capture starts (run_impl would refuse it before its first launch)
-  if (sched != nullptr && !sched_native(variant, N, E, K, V, M, out, flags))
-    return fail(YUMA_EUNSUPPORTED, "an input schedule is not native for these arguments (yuma_sched_native)");
-  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags))
-    return fail(YUMA_EUNSUPPORTED, "YUMA_RUN_W_U16 is not native for these arguments (yuma_u16_native)");
-  const int hbf = (flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
-  if (hbf && out != nullptr) {  // (a null `out` is run_impl's to refuse)
-    if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
-    if (!hist_bf16_native(variant, N, E, V, M, out, flags))
-      return fail(YUMA_EUNSUPPORTED,
-                  "YUMA_RUN_HIST_BF16 is not native for these arguments (yuma_hist_bf16_native)");
-  }
+  RunPlan p;
+  if (const int err = run_plan(q, &p)) return err;  // nothing is refused inside an open capture
   hipStream_t cs = nullptr;
   if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess)
     return fail(YUMA_EHIP, "capture stream creation failed");
@@ -6470,8 +6470,9 @@ int graph_create_impl(yuma_graph_t* graph, const RunOpts& o, int variant, const 
     (void)hipStreamDestroy(cs);
     return fail(YUMA_EHIP, "hipStreamBeginCapture failed");
   }
-  const int rc = run_with(o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                          workspace_bytes, chunk_epochs, cs, nullptr, sched, K);
+  q.stream = cs;
+  q.phase_ms = nullptr;
+  const int rc = q.w_u16 ? run_impl<uint16_t>(q, p) : run_impl<float>(q, p);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(cs, &g);
   (void)hipStreamDestroy(cs);
@@ -6502,32 +6503,29 @@ int yuma_run(int variant, const yuma_params_t* params_dev, int N, int E, int V, 
              const float* W, const float* S, const float* B_init, const float* Wprev_init,
              const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
              int chunk_epochs, void* stream) {
-  return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream);
+  return run_direct(RunReq{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                           workspace_bytes, chunk_epochs, stream, nullptr});
 }
 
 int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                 const float* W, const float* S, const float* B_init, const float* Wprev_init,
                 const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                 int chunk_epochs, int flags, void* stream, float* phase_ms) {
-  if (flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
-  const int wsh = (flags & YUMA_RUN_SHARED_INPUTS) ? 1 : 0;
-  const int hbf = (flags & YUMA_RUN_HIST_BF16) ? 1 : 0;
-  if (flags & YUMA_RUN_W_U16)
-    return run_impl(variant, params_dev, N, E, V, M, reinterpret_cast<const uint16_t*>(W), S, B_init,
-                    Wprev_init, out, workspace, workspace_bytes, chunk_epochs, stream, phase_ms, wsh, 1, 0, hbf);
-  return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream, phase_ms, wsh, 1, 0, hbf);
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  const yuma_run_options_t o{flags};
+  if (const int err = read_opts(&o, &q)) return err;
+  return run_direct(q);
 }
 
 int yuma_run_opts(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                   const float* W, const float* S, const float* B_init, const float* Wprev_init,
                   const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                   int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunOpts o;
-  if (const int err = read_opts(opts, &o)) return err;
-  return run_with(o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-                  chunk_epochs, stream, phase_ms);
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  return run_direct(q);
 }
 
 size_t yuma_workspace_bytes_sched(int variant, int N, int E, int K, int V, int M, int full_outputs) {
@@ -6540,11 +6538,11 @@ int yuma_run_sched(int variant, const yuma_params_t* params_dev, int N, int E, i
                    const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
                    const float* Wprev_init, const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                    int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunOpts o;
-  if (const int err = read_opts(opts, &o)) return err;
-  if (const int err = check_sched(sched_dev, K)) return err;
-  return run_with(o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-                  chunk_epochs, stream, phase_ms, sched_dev, K);
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  if (const int err = read_sched(sched_dev, K, &q)) return err;
+  return run_direct(q);
 }
 
 int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma_outputs_t* out, int flags) {
@@ -6571,16 +6569,16 @@ int yuma_run_profiled(int variant, const yuma_params_t* params_dev, int N, int E
                       const float* Wprev_init, const yuma_outputs_t* out, void* workspace,
                       size_t workspace_bytes, int chunk_epochs, void* stream, float* phase_ms) {
   if (phase_ms == nullptr) return fail(YUMA_EINVAL, "phase_ms is required");
-  return run_impl(variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                  workspace_bytes, chunk_epochs, stream, phase_ms);
+  return run_direct(RunReq{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
+                           workspace_bytes, chunk_epochs, stream, phase_ms});
 }
 
 int yuma_epoch(int variant, const yuma_params_t* params_dev, int N, int V, int M,
                const float* W, const float* W_prev, const float* S, const float* B_old,
                const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                void* stream) {
-  return run_impl(variant, params_dev, N, 1, V, M, W, S, B_old, W_prev, out, workspace,
-                  workspace_bytes, 1, stream);
+  return run_direct(RunReq{variant, params_dev, N, 1, V, M, W, S, B_old, W_prev, out, workspace,
+                           workspace_bytes, 1, stream, nullptr});
 }
 
 int yuma_synth_weights(uint64_t seed, int E, int N, int V, int M, int t0, float* W,
@@ -6610,10 +6608,10 @@ int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t
                            const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                            void* workspace, size_t workspace_bytes, int chunk_epochs,
                            const yuma_run_options_t* opts) {
-  RunOpts o;
-  if (const int err = read_opts(opts, &o)) return err;
-  return graph_create_impl(graph, o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                           workspace_bytes, chunk_epochs);
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  return graph_create_impl(graph, q);
 }
 
 int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
@@ -6621,30 +6619,30 @@ int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_
                             const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                             void* workspace, size_t workspace_bytes, int chunk_epochs,
                             const yuma_run_options_t* opts) {
-  RunOpts o;
-  if (const int err = read_opts(opts, &o)) return err;
-  if (const int err = check_sched(sched_dev, K)) return err;
-  return graph_create_impl(graph, o, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                           workspace_bytes, chunk_epochs, sched_dev, K);
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  if (const int err = read_sched(sched_dev, K, &q)) return err;
+  return graph_create_impl(graph, q);
 }
 
 int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
                          int E, int V, int M, const float* W, const float* S,
                          const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                          void* workspace, size_t workspace_bytes, int chunk_epochs, int flags) {
-  if (flags & ~kRunFlags) return fail(YUMA_EINVAL, "unknown run flags 0x%x", flags);
-  yuma_run_options_t o{};
-  o.flags = flags;
-  return yuma_graph_create_opts(graph, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out,
-                                workspace, workspace_bytes, chunk_epochs, &o);
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  const yuma_run_options_t o{flags};
+  if (const int err = read_opts(&o, &q)) return err;
+  return graph_create_impl(graph, q);
 }
 
 int yuma_graph_create(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
                       int E, int V, int M, const float* W, const float* S,
                       const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                       void* workspace, size_t workspace_bytes, int chunk_epochs) {
-  return yuma_graph_create_ex(graph, variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out,
-                              workspace, workspace_bytes, chunk_epochs, 0);
+  return graph_create_impl(graph, RunReq{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out,
+                                         workspace, workspace_bytes, chunk_epochs, nullptr, nullptr});
 }
 
 int yuma_graph_launch(yuma_graph_t graph, void* stream) {

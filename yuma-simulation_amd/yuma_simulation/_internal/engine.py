@@ -645,6 +645,111 @@ def workspace_bytes(variant: int, N: int, E: int, V: int, M: int, full: bool) ->
     return int(load_library().yuma_workspace_bytes(variant, N, E, V, M, 1 if full else 0))
 
 
+def _vector_form(W: torch.Tensor, w_u16: bool, B_init, Wprev_init, o: dict, hist_bf16: bool) -> bool:
+    """The scan's vector form as the engine tests it (vector_form of the engine
+    source): W on its vector alignment (16 bytes, 8 as uint16), every fp32
+    matrix read or written 16-byte aligned, a bfloat16 history 8-byte. A view
+    at an odd offset sends an fp32 run to the scalar scan, which the uint16,
+    bfloat16-history and schedule kernels lack."""
+    hist = o.get("B_hist")
+    if hist is not None and hist.data_ptr() % (8 if hist_bf16 else 16):
+        return False
+    mats = [B_init, Wprev_init] + [o.get(k) for k in ("Wn", "Wc", "Wb", "B_inst", "B_final")]
+    return W.data_ptr() % (8 if w_u16 else 16) == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in mats)
+
+
+def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_inputs, hist_stride, hist_first,
+                hist_dtype, sched):
+    """run's argument checks, in the order run has always raised them: the
+    history type and the schedule before anything touches a GPU, the rest
+    behind device(). Returns (dev, N, E, K, sched_host, h_epochs); K and
+    sched_host are None without a schedule."""
+    if hist_dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"hist_dtype={hist_dtype} must be None, torch.float32 or torch.bfloat16")
+    if hist_dtype == torch.bfloat16 and single_call:
+        raise ValueError("single_call (yuma_epoch) writes an fp32 history: no hist_dtype=torch.bfloat16")
+    E, Nw, V, M = W.shape
+    K = sched_host = None
+    if sched is not None:  # validated before anything touches a GPU
+        K = E
+        sched_host = _sched_host(sched, K)
+        E = sched_host.numel()
+        for name, t in (out or {}).items():  # a caller's per-epoch outputs follow the schedule's length
+            if t is not None and name not in ("B_hist", "B_final") and t.shape[0] != E:
+                raise ValueError(f"out[{name!r}] holds {t.shape[0]} epochs, the schedule {E}")
+        if S.shape != (K, Nw, V):
+            raise ValueError(f"S shape {tuple(S.shape)} is not [K={K}, N={Nw}, V={V}] of W {tuple(W.shape)}")
+    check_limits(V, M)
+    dev = device()
+    if sched is None and S.shape != (E, Nw, V):
+        raise ValueError(f"S shape {tuple(S.shape)} does not match W {tuple(W.shape)}")
+    N = len(params) if shared_inputs else Nw
+    h_epochs = hist_epochs(E, hist_stride, hist_first)
+    if len(h_epochs) != E and single_call:  # (stride 1 from epoch 0 stores all E epochs: the dense history)
+        raise ValueError("single_call (yuma_epoch) keeps the dense history: no hist_stride / hist_first")
+    for name, t in (("B_init", B_init), ("Wprev_init", Wprev_init)):
+        # the kernels index it n * V * M + row * M + m: a smaller tensor is read past its end
+        if t is not None and tuple(t.shape) != (N, V, M):
+            raise ValueError(f"{name} shape {tuple(t.shape)} is not [N={N}, V={V}, M={M}]")
+    if shared_inputs:
+        if Nw != 1:
+            raise ValueError("shared_inputs takes W [E,1,V,M] and S [E,1,V]")
+        if single_call:
+            raise ValueError("single_call does not take shared inputs")
+    elif len(params) != N:
+        raise ValueError("one parameter record per scenario is required")
+    return dev, N, E, K, sched_host, h_epochs
+
+
+def _alloc_history(o: dict, dev, shape, *, want_hist: bool, h_bf16: bool, native_ok) -> bool:
+    """The history decision, up to alignment: o["B_hist"] checked or allocated
+    ([n_hist, N, V, M]), bfloat16 where the scan is to write it itself. Returns
+    that: hist_dtype=torch.bfloat16, a history with at least one slot, and
+    native_ok() (hist_bf16_native)."""
+    hist_user = o.get("B_hist") if h_bf16 else None  # the caller's bfloat16 buffer
+    if hist_user is not None and hist_user.dtype != torch.bfloat16:
+        raise ValueError(f"out['B_hist'] is {hist_user.dtype}, hist_dtype=torch.bfloat16 needs a bfloat16 tensor")
+    # (a history of no slots is a null pointer to the engine: nothing to write in either type)
+    native = h_bf16 and (want_hist or hist_user is not None) and shape[0] > 0 and native_ok()
+    if want_hist and o.get("B_hist") is None:
+        o["B_hist"] = torch.empty(shape, dtype=torch.bfloat16 if native else torch.float32, device=dev)
+    if o.get("B_hist") is not None and tuple(o["B_hist"].shape) != shape:
+        # the kernels index it slot * N * V * M + ...: a smaller tensor is written past its end
+        raise ValueError(f"out['B_hist'] shape {tuple(o['B_hist'].shape)} is not "
+                         f"[n_hist={shape[0]}, N={shape[1]}, V={shape[2]}, M={shape[3]}]")
+    return native
+
+
+_OUT_SHAPES = {
+    "Dn": "ENV", "C": "ENM", "I": "ENM", "B_final": "NVM",
+    "D": "ENV", "R": "ENM", "P": "ENM", "T": "ENM", "Tv": "ENV", "Sn": "ENV", "bond_alpha": "ENM", "alpha_ab": "EN2",
+    "Wn": "ENVM", "Wc": "ENVM", "Wb": "ENVM", "B_inst": "ENVM",
+}
+
+
+def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms) -> None:
+    """The run's one launch: yuma_run_opts, or yuma_run_sched under a native
+    schedule; with `capture`, their yuma_graph_create_* twins, the handle
+    appended to it. head: variant, params, N, E; tail: V, M ... chunk_epochs."""
+    if sched_dev is None:
+        run_fn, graph_fn, args = lib.yuma_run_opts, lib.yuma_graph_create_opts, head + tail
+    else:  # E and K in place of E, the schedule after S
+        run_fn, graph_fn = lib.yuma_run_sched, lib.yuma_graph_create_sched
+        args = head + (K,) + tail[:4] + (sched_dev.data_ptr(),) + tail[4:]
+    args += (ctypes.addressof(opts),)
+    if capture is not None:  # RunGraph: capture instead of launching
+        h = ctypes.c_void_p()
+        torch.cuda.synchronize(dev)
+        _check(graph_fn(ctypes.byref(h), *args), graph_fn.__name__)
+        capture.append(h)
+        return
+    # phase_ms (bench-only): per-phase device time from HIP events (blocks)
+    buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
+    _check(run_fn(*args, torch.cuda.current_stream(dev).cuda_stream, buf), run_fn.__name__)
+    if phase_ms is not None:
+        phase_ms[:] = list(buf)
+
+
 def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tensor,
         B_init: torch.Tensor | None = None, Wprev_init: torch.Tensor | None = None, *,
         want_hist: bool = False, want: tuple[str, ...] = (), chunk_epochs: int = 0,
@@ -655,10 +760,10 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
-    yumas.py:61/175/285/399/494) instead of yuma_run.
+    yumas.py:61/175/285/399/494) instead of yuma_run_opts.
     shared_inputs: W [E,1,V,M] and S [E,1,V] are one trajectory that every
     scenario (one per params record) reads — a parameter sweep over one subnet
-    (yuma_run_ex, YUMA_RUN_SHARED_INPUTS); results equal a run on W and S
+    (YUMA_RUN_SHARED_INPUTS); results equal a run on W and S
     replicated per scenario.
     hist_stride, hist_first: with want_hist (or out["B_hist"]), store the bond
     state after the epochs hist_epochs(E, hist_stride, hist_first) only:
@@ -685,46 +790,12 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     and under single_call, the inputs are expanded on the device and the dense
     path runs (extra["sched_path"] == "expanded"; a captured run raises
     EngineError instead)."""
-    if hist_dtype not in (None, torch.float32, torch.bfloat16):
-        raise ValueError(f"hist_dtype={hist_dtype} must be None, torch.float32 or torch.bfloat16")
     h_bf16 = hist_dtype == torch.bfloat16
-    if h_bf16 and single_call:
-        raise ValueError("single_call (yuma_epoch) writes an fp32 history: no hist_dtype=torch.bfloat16")
-    E, Nw, V, M = W.shape
-    sched_host = None
-    if sched is not None:  # validated before anything touches a GPU
-        K = E
-        sched_host = _sched_host(sched, K)
-        E = sched_host.numel()
-        for name, t in (out or {}).items():  # a caller's per-epoch outputs follow the schedule's length
-            if t is not None and name not in ("B_hist", "B_final") and t.shape[0] != E:
-                raise ValueError(f"out[{name!r}] holds {t.shape[0]} epochs, the schedule {E}")
-        if S.shape != (K, Nw, V):
-            raise ValueError(f"S shape {tuple(S.shape)} is not [K={K}, N={Nw}, V={V}] of W {tuple(W.shape)}")
-    check_limits(V, M)
-    dev = device()
+    dev, N, E, K, sched_host, h_epochs = _check_args(
+        params, W, S, B_init, Wprev_init, out, single_call=single_call, shared_inputs=shared_inputs,
+        hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched)
+    V, M = W.shape[2:]
     lib = load_library()
-    if sched is None and S.shape != (E, Nw, V):
-        raise ValueError(f"S shape {tuple(S.shape)} does not match W {tuple(W.shape)}")
-    n_scen = len(params) if shared_inputs else Nw
-    h_epochs = hist_epochs(E, hist_stride, hist_first)
-    strided = len(h_epochs) != E  # stride 1 from epoch 0 stores all E epochs: the dense history
-    if strided and single_call:
-        raise ValueError("single_call (yuma_epoch) keeps the dense history: no hist_stride / hist_first")
-    for name, t in (("B_init", B_init), ("Wprev_init", Wprev_init)):
-        # the kernels index it n * V * M + row * M + m: a smaller tensor is read past its end
-        if t is not None and tuple(t.shape) != (n_scen, V, M):
-            raise ValueError(f"{name} shape {tuple(t.shape)} is not [N={n_scen}, V={V}, M={M}]")
-    if shared_inputs:
-        if Nw != 1:
-            raise ValueError("shared_inputs takes W [E,1,V,M] and S [E,1,V]")
-        N = len(params)
-        if single_call:
-            raise ValueError("single_call does not take shared inputs")
-    else:
-        N = Nw
-        if len(params) != N:
-            raise ValueError("one parameter record per scenario is required")
     # uint16 weights stay 16-bit on the device where the engine reads them
     # natively (u16_native); anywhere else they are widened like any dtype
     w_u16 = False
@@ -740,71 +811,40 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     Wprev_init = None if Wprev_init is None else _as_dev(Wprev_init, dev)
     prm = params_tensor(params, dev)
     o = {} if out is None else dict(out)
+    sizes = {"E": E, "N": N, "V": V, "M": M, "2": 2}
 
-    def need(name, shape):
-        if name not in o or o[name] is None:
-            o[name] = torch.empty(shape, dtype=torch.float32, device=dev)
+    def need(name):
+        if o.get(name) is None:
+            o[name] = torch.empty(tuple(sizes[d] for d in _OUT_SHAPES[name]), dtype=torch.float32, device=dev)
 
-    need("Dn", (E, N, V))
-    need("C", (E, N, M))
-    need("I", (E, N, M))
-    need("B_final", (N, V, M))
-    hist_user = o.get("B_hist") if h_bf16 else None  # the caller's bfloat16 buffer
-    if hist_user is not None and hist_user.dtype != torch.bfloat16:
-        raise ValueError(f"out['B_hist'] is {hist_user.dtype}, hist_dtype=torch.bfloat16 needs a bfloat16 tensor")
-    # (a history of no slots is a null pointer to the engine: nothing to write in either type)
-    hist_native = (h_bf16 and (want_hist or hist_user is not None) and len(h_epochs) > 0
-                   and hist_bf16_native(variant, N, E, V, M, shared_inputs=shared_inputs)
-                   and (hist_user is None or hist_user.data_ptr() % 8 == 0))
-    if want_hist and hist_native and hist_user is None:
-        o["B_hist"] = torch.empty((len(h_epochs), N, V, M), dtype=torch.bfloat16, device=dev)
-    if want_hist:
-        need("B_hist", (len(h_epochs), N, V, M))
-    if o.get("B_hist") is not None:
-        # the kernels index it slot * N * V * M + ...: a smaller tensor is written past its end
-        if tuple(o["B_hist"].shape) != (len(h_epochs), N, V, M):
-            raise ValueError(f"out['B_hist'] shape {tuple(o['B_hist'].shape)} is not "
-                             f"[n_hist={len(h_epochs)}, N={N}, V={V}, M={M}]")
-    shapes = {
-        "D": (E, N, V), "R": (E, N, M), "P": (E, N, M), "T": (E, N, M), "Tv": (E, N, V),
-        "Sn": (E, N, V), "bond_alpha": (E, N, M), "alpha_ab": (E, N, 2),
-        "Wn": (E, N, V, M), "Wc": (E, N, V, M), "Wb": (E, N, V, M), "B_inst": (E, N, V, M),
-    }
+    for name in ("Dn", "C", "I", "B_final"):
+        need(name)
+    hist_user = o.get("B_hist") if h_bf16 else None  # the caller's bfloat16 buffer: the result goes there
+    hist_native = _alloc_history(
+        o, dev, (len(h_epochs), N, V, M), want_hist=want_hist, h_bf16=h_bf16,
+        native_ok=lambda: hist_bf16_native(variant, N, E, V, M, shared_inputs=shared_inputs))
     for name in want:
-        need(name, shapes[name])
+        need(name)
     if "T" in o and "P" not in o:
-        need("P", shapes["P"])
-    if hist_native:
-        # the scan's vector form, as the engine tests it: W and every fp32
-        # matrix on its vector alignment (an odd view sends the run to the
-        # scalar scan, which writes an fp32 history only)
-        mats = [B_init, Wprev_init] + [o.get(k) for k in ("B_final", "Wn", "Wc", "Wb", "B_inst")]
-        if W.data_ptr() % (8 if w_u16 else 16) or any(t is not None and t.data_ptr() % 16 for t in mats):
-            hist_native = False
+        need("P")
+    # the three native paths need the vector form; each falls back where a buffer is off its alignment
+    hist_native = hist_native and _vector_form(W, w_u16, B_init, Wprev_init, o, True)
     if h_bf16 and o.get("B_hist") is not None and not hist_native:
         if capture is not None:
             raise EngineError("a captured run cannot convert an fp32 history: hist_dtype=torch.bfloat16 needs "
                               "hist_bf16_native(variant, N, E, V, M), a stored epoch and vector-aligned buffers")
         if o["B_hist"].dtype != torch.float32:  # the run's fp32 history, converted below
             o["B_hist"] = torch.empty((len(h_epochs), N, V, M), dtype=torch.float32, device=dev)
-    full = o.get("Tv") is not None
-    if w_u16:
-        # the fp32 matrices of the vector paths: a view at an odd offset sends
-        # the fp32 run to its scalar loads, which the uint16 kernels lack
-        mats = [B_init, Wprev_init, o.get("B_final")] + ([] if hist_native else [o.get("B_hist")])
-        if any(t is not None and t.data_ptr() % 16 for t in mats):
-            w_u16 = False
-            W = _as_dev(W, dev)
+    if w_u16 and not _vector_form(W, True, B_init, Wprev_init, o, hist_native):
+        w_u16 = False
+        W = _as_dev(W, dev)
     sched_dev = None
     if sched is not None:
         names = tuple(k for k, v in o.items() if v is not None and k != "B_hist")
-        native = (not single_call
-                  and sched_native(variant, N, E, K, V, M, o.get("B_hist") is not None, names,
-                                   shared_inputs=shared_inputs))
-        if native:  # the vector form, as the engine tests it
-            mats = [B_init, Wprev_init, o.get("B_final")] + ([] if hist_native else [o.get("B_hist")])
-            native = not (W.data_ptr() % (8 if w_u16 else 16) or any(t is not None and t.data_ptr() % 16 for t in mats))
-        if native:
+        if (not single_call
+                and sched_native(variant, N, E, K, V, M, o.get("B_hist") is not None, names,
+                                 shared_inputs=shared_inputs)
+                and _vector_form(W, w_u16, B_init, Wprev_init, o, hist_native)):
             if (isinstance(sched, torch.Tensor) and sched.device == dev and sched.dtype == torch.int32
                     and sched.is_contiguous()):
                 sched_dev = sched  # the caller's tensor: a captured run follows its in-place updates
@@ -815,6 +855,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                 raise EngineError("a captured run cannot expand its inputs: sched= needs "
                                   "sched_native(variant, N, E, K, V, M, ...) and vector-aligned buffers")
             W, S = _take_slices(W, sched_host.to(dev)), _take_slices(S, sched_host.to(dev))
+    full = o.get("Tv") is not None
     if sched_dev is not None:
         nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
     else:
@@ -822,77 +863,21 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     if workspace is None or workspace.numel() < nbytes:
         workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     outs = YumaOutputsC(**{k: _ptr(o.get(k)) for k in OUTPUT_FIELDS})
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    args = (variant, prm.data_ptr(), N, E, V, M, W.data_ptr(), S.data_ptr(),
-            _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
-            workspace.data_ptr(), workspace.numel(), int(chunk_epochs), stream)
-    if sched_dev is not None:  # yuma_run_sched / yuma_graph_create_sched, with every option of the run
-        opts = YumaRunOptionsC(flags=(RUN_W_U16 if w_u16 else 0) | (RUN_HIST_BF16 if hist_native else 0),
-                               hist_stride=min(int(hist_stride), E), hist_first=h_epochs[0] if h_epochs else E)
-        sargs = args[:4] + (K,) + args[4:8] + (sched_dev.data_ptr(),) + args[8:14] + (ctypes.addressof(opts),)
-        if capture is not None:
-            h = ctypes.c_void_p()
-            torch.cuda.synchronize(dev)
-            _check(lib.yuma_graph_create_sched(ctypes.byref(h), *sargs), "yuma_graph_create_sched")
-            capture.append(h)
-        else:
-            buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
-            _check(lib.yuma_run_sched(*sargs, stream, buf), "yuma_run_sched")
-            if phase_ms is not None:
-                phase_ms[:] = list(buf)
-    elif strided or hist_native:  # yuma_run_opts / yuma_graph_create_opts: the history options, with the run's flags
-        opts = YumaRunOptionsC(flags=(RUN_W_U16 if w_u16 else 0) | (RUN_SHARED_INPUTS if shared_inputs else 0)
-                               | (RUN_HIST_BF16 if hist_native else 0),
-                               # (a stride of E or more stores one epoch at the most: int32 either way)
-                               hist_stride=min(int(hist_stride), E), hist_first=h_epochs[0] if h_epochs else E)
-        if capture is not None:
-            h = ctypes.c_void_p()
-            torch.cuda.synchronize(dev)
-            _check(lib.yuma_graph_create_opts(ctypes.byref(h), *args[:-1], ctypes.addressof(opts)),
-                   "yuma_graph_create_opts")
-            capture.append(h)
-        else:
-            buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
-            _check(lib.yuma_run_opts(*args[:-1], ctypes.addressof(opts), stream, buf), "yuma_run_opts")
-            if phase_ms is not None:
-                phase_ms[:] = list(buf)
-    elif w_u16:  # yuma_run_ex / yuma_graph_create_ex with YUMA_RUN_W_U16
-        if capture is not None:
-            h = ctypes.c_void_p()
-            torch.cuda.synchronize(dev)
-            _check(lib.yuma_graph_create_ex(ctypes.byref(h), *args[:-1], RUN_W_U16), "yuma_graph_create_ex")
-            capture.append(h)
-        else:
-            buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
-            _check(lib.yuma_run_ex(*args[:-1], RUN_W_U16, stream, buf), "yuma_run_ex")
-            if phase_ms is not None:
-                phase_ms[:] = list(buf)
-    elif single_call:  # one Yuma* call per slice: the yuma_epoch entry point
+    if single_call:  # one Yuma* call per slice: the yuma_epoch entry point
         if E != 1 or capture is not None or phase_ms is not None:
             raise ValueError("single_call is one epoch, launched directly")
         _check(lib.yuma_epoch(variant, prm.data_ptr(), N, V, M, W.data_ptr(), _ptr(Wprev_init),
                               S.data_ptr(), _ptr(B_init), ctypes.addressof(outs), workspace.data_ptr(),
-                              workspace.numel(), stream), "yuma_epoch")
-    elif capture is not None:  # RunGraph: capture instead of launching
-        h = ctypes.c_void_p()
-        torch.cuda.synchronize(dev)
-        if shared_inputs:
-            _check(lib.yuma_graph_create_ex(ctypes.byref(h), *args[:-1], RUN_SHARED_INPUTS),
-                   "yuma_graph_create_ex")
-        else:
-            _check(lib.yuma_graph_create(ctypes.byref(h), *args[:-1]), "yuma_graph_create")
-        capture.append(h)
-    elif shared_inputs:
-        buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
-        _check(lib.yuma_run_ex(*args[:-1], RUN_SHARED_INPUTS, stream, buf), "yuma_run_ex")
-        if phase_ms is not None:
-            phase_ms[:] = list(buf)
-    elif phase_ms is None:
-        _check(lib.yuma_run(*args), "yuma_run")
-    else:  # bench-only: per-phase device time from HIP events (blocks)
-        buf = (ctypes.c_float * len(PHASES))()
-        _check(lib.yuma_run_profiled(*args, buf), "yuma_run_profiled")
-        phase_ms[:] = list(buf)
+                              workspace.numel(), torch.cuda.current_stream(dev).cuda_stream), "yuma_epoch")
+    else:
+        opts = YumaRunOptionsC(flags=(RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+                               | (RUN_HIST_BF16 if hist_native else 0),
+                               # (a stride of E or more stores one epoch at the most: int32 either way)
+                               hist_stride=min(int(hist_stride), E), hist_first=h_epochs[0] if h_epochs else E)
+        _launch(lib, dev, (variant, prm.data_ptr(), N, E), K, sched_dev,
+                (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
+                 workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
+                capture=capture, phase_ms=phase_ms)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -908,7 +893,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
 
 
 class RunGraph:
-    """A whole `run` captured once into a HIP graph (yuma_graph_create) and
+    """A whole `run` captured once into a HIP graph (yuma_graph_create_opts) and
     replayed with one launch per call: the E-epoch loop of run_simulation
     (simulation_utils.py:52-110) with no host work between phases or epochs.
     Inputs and outputs are the buffers of the capture (`result`); refill the
