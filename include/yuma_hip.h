@@ -302,6 +302,60 @@ int yuma_run_sched(int variant, const yuma_params_t* params_dev, int N, int E, i
 int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma_outputs_t* out,
                       int flags);
 
+/* ------------------------------------------------------------------------
+ * Watched bond columns: the bond history of a few miner columns.
+ *
+ * The charts that read a bond history plot a handful of servers (miner
+ * columns); a [V][M] history per stored epoch is hundreds of times what they
+ * read. yuma_run_watch takes a list watch_dev [n_watch] of miner columns in
+ * DEVICE memory and writes B_watch [n_hist][N][V][n_watch] (fp32), n_hist =
+ * yuma_hist_slots(E, stride, first) under the options' history stride and
+ * first epoch, which apply to it as they do to B_hist: slot s, column j holds
+ * the bits the dense history holds at [epoch t_s][n][v][watch_dev[j]].
+ * Duplicated and unsorted columns are allowed. out->B_hist may be NULL -- the
+ * intended use: the main run then takes its history-less scans, and a small
+ * kernel of its own recomputes the watched elements from the per-epoch vectors
+ * phase 1 leaves in the workspace (counted under YUMA_PHASE_BONDS) -- or
+ * non-NULL: both histories are written. YUMA_RUN_HIST_BF16 concerns B_hist
+ * only; B_watch is fp32. Every other output, B_final included, has the bits of
+ * the same run without a watch list.
+ *
+ * The arguments are yuma_run_sched's with watch_dev, n_watch and B_watch after
+ * `out`. sched_dev == NULL with K == 0 means no schedule: W is [E][N][V][M],
+ * S [E][N][V] and the workspace yuma_workspace_bytes. With a schedule they are
+ * exactly yuma_run_sched's and the workspace is yuma_workspace_bytes_sched.
+ * The watch list needs no workspace of its own.
+ *
+ * Native (yuma_watch_native returns 1; host only, `flags` are the run's
+ * flags): Yuma 3 and Yuma 4 (scalar or liquid alpha, any reset mode), any V up
+ * to YUMA_MAX_VALIDATORS, any M and any alignment (the kernel has scalar
+ * accesses only), no YUMA_RUN_SHARED_INPUTS; with YUMA_RUN_W_U16 where
+ * yuma_u16_native holds. Elsewhere the entry points return YUMA_EUNSUPPORTED
+ * before the first launch and the caller gathers the columns of an fp32
+ * history itself.
+ *
+ * The host cannot check a list in device memory without a synchronisation:
+ * the kernel clamps every entry into [0, M) before it addresses anything, so a
+ * bad list gives unspecified numbers and never an access outside W. A graph
+ * re-reads the list at every replay: rewrite it in place between replays like
+ * any other input.
+ *
+ * Refusals, in this order, all before the first launch and without a HIP call
+ * (yuma_graph_create_watch: the same code and yuma_last_error text, before the
+ * capture opens): the options (as yuma_run_opts); [the graph handle]; sizes;
+ * NULL params / W / S / out / workspace; a schedule pointer with K < 1, or
+ * K != 0 without one (YUMA_EINVAL); n_watch < 1, then a NULL watch_dev or
+ * B_watch (YUMA_EINVAL); the workspace size; the schedule not native; the
+ * watch list not native (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and
+ * YUMA_RUN_W_U16 as ever. yuma_epoch and yuma_shard_stage take no watch list.
+ * ---------------------------------------------------------------------- */
+int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                   const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                   const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
+                   int n_watch, float* B_watch, void* workspace, size_t workspace_bytes,
+                   int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms);
+int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags);
+
 /* hipGraph form of yuma_run: the whole multi-epoch run (every phase of every
  * chunk, no host work between them) captured once into a HIP graph and
  * replayed with one hipGraphLaunch. The arguments are those of yuma_run and
@@ -337,6 +391,13 @@ int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_
                             int E, int K, int V, int M, const float* W, const float* S,
                             const int32_t* sched_dev, const float* B_init, const float* Wprev_init,
                             const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
+                            int chunk_epochs, const yuma_run_options_t* opts);
+/* yuma_graph_create_sched with a watch list (yuma_run_watch's arguments). */
+int yuma_graph_create_watch(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                            int E, int K, int V, int M, const float* W, const float* S,
+                            const int32_t* sched_dev, const float* B_init, const float* Wprev_init,
+                            const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                            float* B_watch, void* workspace, size_t workspace_bytes,
                             int chunk_epochs, const yuma_run_options_t* opts);
 /* Replay on `stream` (stream-ordered, no host synchronisation). */
 int yuma_graph_launch(yuma_graph_t graph, void* stream);

@@ -4508,6 +4508,160 @@ __global__ __launch_bounds__(256) void k_sched_expand(ExpandArgs X) {
 }
 
 // ---------------------------------------------------------------------------
+// Watched bond columns (yuma_run_watch): the bond history of a few miner
+// columns, every stored epoch in fp32, without a [V][M] history. Yuma 3 / Yuma 4
+// are element-wise: element (v, m) of the state depends on its own past,
+// W[t][n][v][m], the row's sum and stake and column m's incentive / liquid
+// bond_alpha, all of which phase 1 has left in per-epoch arrays for the whole
+// chunk. So a kernel of its own recomputes the watched elements, and the main
+// scan stays the history-less one with its code untouched (a lane-dependent
+// store inside k_bonds_elem cost 1.65 -> 2.71 ms, a run-time option 132 -> 456
+// spilled VGPRs: see there). It runs on the run's stream before the chunk's
+// main scan, which overwrites Bstate at its end.
+//   One thread owns one (scenario n, row v, watched index j) element, j
+//   fastest, then v; a block belongs to one scenario (its parameters are block-
+//   uniform), so the [V][n_watch] block of a stored slot goes out as contiguous
+//   4-byte stores. The column is clamp(watch[j], 0, M - 1), read once: the
+//   host cannot check device memory, a bad list gives unspecified numbers and
+//   never an access outside W.
+//   The thread count is tiny (256 x 8 at the headline shape), so the kernel is
+//   bound by the latency of its dependent chain, not by bytes: one wave per
+//   block spreads the waves over the CUs, and the inputs of an epoch (the
+//   weight, the row's sum and stake, the column's liquid bond_alpha; the
+//   incentive enters the dividends only, which the main scan forms) sit in a
+//   register ring kWatchP epochs deep (an unpipelined loop pays one HBM round
+//   trip per epoch; an epoch's arithmetic is a few hundred cycles, an HBM
+//   miss about 900 on an idle chip and a multiple under the load of the other
+//   waves, so 8 epochs in flight cover it at 32 ring registers).
+//   Arithmetic: the torch-order form that k_bonds_elem documents as its bit
+//   reference (IEEE w / rd, tmin / tmax, Yuma 3's cap clamp as tmin(nb, cap))
+//   and its reset rule; every parameter and the conditional reset's test are
+//   read before the loop, for the reason given there.
+//   History: BondArgs' countdown (hnext / hslot / hstride, resolved per chunk by
+//   the same host code; the dense history is stride 1); slot s goes to
+//   B_watch[s][n][v][j] on a test of t alone.
+// ---------------------------------------------------------------------------
+constexpr int kWatchP = 8;    // epochs of inputs in flight
+constexpr int kWatchBS = 64;  // threads per block: one wave
+struct WatchArgs {
+  const void* W;  // fp32 or (WT = uint16_t) uint16 elements; [E][N][V][M], or [K][N][V][M] under SC
+  const float* rsd;
+  const float* sn;
+  const float* C;
+  const float* ba;
+  const yuma_params_t* prm;
+  const float* B_init;
+  const float* Bstate;   // [N][V][M], the state before epoch t0 when t0 > 0
+  const int32_t* watch;  // [nw] device memory
+  float* B_watch;        // [n_hist][N][V][nw]
+  const int32_t* sched;  // SC: [E] device memory
+  int K;                 // SC: stored slices
+  int N, V, M, nw, t0, t1;
+  int bps;  // blocks per scenario
+  int hstride, hnext, hslot;
+};
+template <int VARIANT, typename WT, bool SC>
+__global__ __launch_bounds__(kWatchBS) void k_bonds_watch(WatchArgs A) {
+  static_assert(VARIANT == YUMA_VARIANT_YUMA3 || VARIANT == YUMA_VARIANT_YUMA4, "element-wise variants only");
+  constexpr int P = kWatchP;
+  const int N = A.N, V = A.V, M = A.M, nw = A.nw;
+  const int n = blockIdx.x / A.bps;
+  const long long e = (long long)(blockIdx.x % A.bps) * kWatchBS + threadIdx.x;
+  if (e >= (long long)V * nw) return;
+  const int v = (int)(e / nw), j = (int)(e - (long long)v * nw);
+  const int col = min(max(A.watch[j], 0), M - 1);
+  const long long VM = (long long)V * M;
+  const yuma_params_t& pg = A.prm[n];
+  const bool liquid = pg.liquid_mode != YUMA_LIQUID_OFF;
+  const int reset_mode = pg.reset_mode, reset_epoch = pg.reset_epoch, reset_index = pg.reset_index;
+  const bool reset_all = (pg.flags & YUMA_FLAG_RESET_ALL_COLUMNS) != 0;
+  const float p_bond_alpha = pg.bond_alpha, p_omba = pg.one_minus_bond_alpha;
+  const float p_maxint = pg.maxint, p_capacity_alpha = pg.capacity_alpha, p_decay_keep = pg.decay_keep;
+  // reset_c_zero's test on this record's fields
+  bool zero_c = false;
+  if (reset_mode == YUMA_RESET_IF_ZERO_CONSENSUS && !reset_all && reset_epoch >= 1 && reset_epoch >= A.t0 &&
+      reset_epoch < A.t1 && reset_index >= 0 && reset_index < M)
+    zero_c = A.C[((long long)(reset_epoch - 1) * N + n) * M + reset_index] == 0.0f;
+  const WT* const Wa = static_cast<const WT*>(A.W);
+
+  const float* src = A.t0 == 0 ? A.B_init : A.Bstate;
+  bool has_old = src != nullptr;
+  float B = has_old ? src[n * VM + (long long)v * M + col] : 0.0f;
+
+  WT rw[P];
+  float rd[P], rsn[P], rba[P];
+  // SC: the stored slice of epoch t, as k_bonds_elem reads it (block-uniform,
+  // a scalar load, clamped into [0, K), t clamped to the launch's last epoch)
+  auto sched_at = [&](int t) -> int {
+    if constexpr (SC) {
+      typedef const __attribute__((address_space(4))) int32_t* cptr;
+      const int tt = __builtin_amdgcn_readfirstlane(min(t, A.t1 - 1));
+      return min(max(__builtin_amdgcn_readfirstlane(((cptr)A.sched)[tt]), 0), A.K - 1);
+    } else {
+      return 0;
+    }
+  };
+  auto fetch = [&](int k, int t, int sk) {
+    const long long slice = (long long)t * N + n;
+    const long long wslice = SC ? (long long)sk * N + n : slice;
+    rw[k] = Wa[wslice * VM + (long long)v * M + col];
+    rd[k] = A.rsd[slice * V + v];
+    rsn[k] = A.sn[slice * V + v];
+    // Yuma 4 reads bond_alpha for every scenario (the array is there for all;
+    // a fixed-alpha scenario ignores the value): no branch around a load
+    if constexpr (VARIANT == YUMA_VARIANT_YUMA4) rba[k] = A.ba[slice * M + col];
+  };
+  int hnext = A.hnext;
+  long long hsl = (long long)A.hslot * N + n;
+  // Every fetch is unconditional, its epoch clamped to the launch's last one
+  // (a fetch past the end re-reads that epoch and is never used): with a
+  // branch around the ring's loads the waitcnt pass drained the whole ring
+  // (vmcnt(0)) once per P epochs, one exposed round trip each time.
+  const int tl = A.t1 - 1;
+#pragma unroll
+  for (int k = 0; k < P; ++k) fetch(k, min(A.t0 + k, tl), sched_at(A.t0 + k));
+  int snext = sched_at(A.t0 + P);
+
+  for (int tb = A.t0; tb < A.t1; tb += P) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+      const int t = tb + k;
+      if (t >= A.t1) break;
+      if (has_old && reset_mode != YUMA_RESET_NONE && t == reset_epoch &&
+          (reset_all || (reset_index >= 0 && reset_index < M))) {
+        bool fire = reset_mode == YUMA_RESET_ALWAYS;
+        if (reset_mode == YUMA_RESET_IF_ZERO_CONSENSUS && t >= 1 && !reset_all) fire = zero_c;
+        if (fire && (reset_all || reset_index == col)) B = 0.0f;
+      }
+      const float wn = wf32(rw[k]) / rd[k];
+      if constexpr (VARIANT == YUMA_VARIANT_YUMA3) {
+        const float cap = rsn[k] * p_maxint;
+        const float ca = p_capacity_alpha * cap;
+        const float rem = tmax(cap - B, 0.0f);
+        const float pc = tmin(ca, rem);
+        const float nb = p_decay_keep * B + pc * wn;
+        B = tmin(nb, cap);
+      } else {
+        const float bac = liquid ? rba[k] : p_bond_alpha;
+        const float omba = liquid ? 1.0f - rba[k] : p_omba;
+        const float bd = B * omba;
+        const float rem = tmax(1.0f - bd, 0.0f);
+        const float nb = bd + tmin(bac * wn, rem);
+        B = tmin(nb, 1.0f);
+      }
+      if (t == hnext) {  // from t alone: the same branch in every thread
+        A.B_watch[(hsl * V + v) * nw + j] = B;
+        hnext += A.hstride;
+        hsl += N;
+      }
+      has_old = true;
+      fetch(k, min(t + P, tl), snext);
+      if constexpr (SC) snext = sched_at(t + P + 1);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Phase 2 for parameter sweeps over ONE input trajectory (shared inputs,
 // config c3), element-wise variants: a block runs the scan of K scenarios
 // side by side over one 16 R-row x 64-miner tile of W. Every scenario of the
@@ -5802,6 +5956,45 @@ int launch_bonds_elem(hipStream_t st, yk::BondArgs& A, const int32_t* sched, int
     return with_bool(hist, [&](auto HIST) { return tile(HIST, std::false_type{}); });
 }
 
+// The watched columns' scan over the chunk of A (k_bonds_watch), from the main
+// scan's own arguments: the same inputs, state and history countdown. Enqueued
+// before that scan, which overwrites A.Bstate.
+template <typename WT>
+void launch_watch(hipStream_t st, int variant, const yk::BondArgs& A, const int32_t* watch, int nw, float* B_watch,
+                  const int32_t* sched, int K) {
+  yk::WatchArgs X{};
+  X.W = A.W;
+  X.rsd = A.rsd;
+  X.sn = A.sn;
+  X.C = A.C;
+  X.ba = A.ba;
+  X.prm = A.prm;
+  X.B_init = A.B_init;
+  X.Bstate = A.Bstate;
+  X.watch = watch;
+  X.B_watch = B_watch;
+  X.sched = sched;
+  X.K = K;
+  X.N = A.N;
+  X.V = A.V;
+  X.M = A.M;
+  X.nw = nw;
+  X.t0 = A.t0;
+  X.t1 = A.t1;
+  X.bps = (int)(((long long)A.V * nw + yk::kWatchBS - 1) / yk::kWatchBS);
+  X.hstride = A.hstride;
+  X.hnext = A.hnext;
+  X.hslot = A.hslot;
+  const long long nblocks = (long long)A.N * X.bps;
+  with_bool(sched != nullptr, [&](auto SC) {
+    constexpr bool kSc = decltype(SC)::value;
+    if (variant == YUMA_VARIANT_YUMA3)
+      YK_LAUNCH((yk::k_bonds_watch<YUMA_VARIANT_YUMA3, WT, kSc>), nblocks, yk::kWatchBS, st, X);
+    else
+      YK_LAUNCH((yk::k_bonds_watch<YUMA_VARIANT_YUMA4, WT, kSc>), nblocks, yk::kWatchBS, st, X);
+  });
+}
+
 // Launch the bond scan for A.N scenarios over epochs [A.t0, A.t1); returns
 // the layout of the dividend partials it wrote (k_finalize / k_dsum read it).
 template <bool VEC>
@@ -5879,6 +6072,18 @@ bool sched_native(int variant, int N, int E, int K, int V, int M, const yuma_out
   if (out != nullptr && (out->Wn || out->Wc || out->Wb || out->B_inst || out->Tv || out->P || out->T)) return false;
   if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags)) return false;
   if ((flags & YUMA_RUN_HIST_BF16) && !hist_bf16_native(variant, N, E, V, M, out, flags)) return false;
+  return true;
+}
+
+// Whether a run with these arguments writes a watched history natively
+// (yuma_watch_native): the element-wise variants, per-scenario inputs. The
+// kernel has scalar accesses only: any M, any alignment, any validator count.
+// With YUMA_RUN_W_U16 in `flags`, where the uint16 weights are native.
+bool watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || V < 1 || M < 1 || n_watch < 1 || V > YUMA_MAX_VALIDATORS) return false;
+  if (flags & YUMA_RUN_SHARED_INPUTS) return false;
+  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, nullptr, flags)) return false;
   return true;
 }
 
@@ -6002,6 +6207,12 @@ struct RunReq {
   // yuma_run_sched: W is [K][N][V][M], S [K][N][V]; epoch t reads stored slice sched[t] ([E], device memory)
   const int32_t* sched = nullptr;
   int K = 0;
+  // yuma_run_watch (has_watch): the watched columns watch[n_watch] (device memory) and their history
+  // B_watch [n_hist][N][V][n_watch]
+  int has_watch = 0;
+  const int32_t* watch = nullptr;
+  int n_watch = 0;
+  float* B_watch = nullptr;
 };
 
 // What run_plan resolves for run_impl: the carved workspace (wk: the staging
@@ -6023,6 +6234,14 @@ int run_plan(const RunReq& q, RunPlan* p) {
   if ((M + yk::kTileM - 1) / yk::kTileM > yk::kMaxTiles) return fail(YUMA_EINVAL, "M too large");
   if (!q.prm || !q.W || !q.S || !out || !q.workspace) return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
   if (q.sched != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
+  if (q.sched == nullptr && K != 0) return fail(YUMA_EINVAL, "K=%d stored slices without a schedule pointer", K);
+  if (q.has_watch) {
+    if (q.n_watch < 1) return fail(YUMA_EINVAL, "n_watch=%d watched columns: at least one is required", q.n_watch);
+    if (q.watch == nullptr || q.B_watch == nullptr) return fail(YUMA_EINVAL, "the watch list or B_watch is NULL");
+    // (k_bonds_watch: one wave per block, N blocks-per-scenario blocks)
+    if (((long long)V * q.n_watch + yk::kWatchBS - 1) / yk::kWatchBS * N > INT_MAX)
+      return fail(YUMA_EINVAL, "n_watch=%d: N V n_watch elements exceed the watch kernel's grid", q.n_watch);
+  }
   const int full = out->Tv != nullptr;
   // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
   // params live in device memory, so the Python marshaller enforces it.
@@ -6046,6 +6265,11 @@ int run_plan(const RunReq& q, RunPlan* p) {
                   "an input schedule (yuma_sched_native) needs the vector form: W vector-aligned and the fp32 "
                   "matrices 16-byte aligned");
   }
+  if (q.has_watch && !watch_native(variant, N, E, V, M, q.n_watch, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
+    return fail(YUMA_EUNSUPPORTED,
+                "a watch list is not native for variant=%d V=%d shared=%d (yuma_watch_native): run the fp32 "
+                "history and gather the columns",
+                variant, V, wsh);
   if (q.hist_bf16) {
     if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
     if (!hist_bf16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
@@ -6251,6 +6475,8 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
       A.hslot = next < E ? (int)j : 0;
     }
     tm.mark(YUMA_PHASE_BONDS);
+    if (q.has_watch)  // (Yuma 3 / Yuma 4: run_plan) the state before epoch c0 is still in A.Bstate
+      launch_watch<WT>(st, variant, A, q.watch, q.n_watch, q.B_watch, sched, K);
     int ptiles = tiles;
     int dpl;
     if (sched != nullptr)  // (Yuma 3 / Yuma 4 in vector form: run_plan)
@@ -6442,6 +6668,17 @@ int read_sched(const int32_t* sched_dev, int K, RunReq* q) {
   return YUMA_OK;
 }
 
+// yuma_run_watch / yuma_graph_create_watch: the schedule (none: NULL and K = 0) and the watch list as given;
+// run_plan refuses what is wrong with them.
+void read_watch(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, RunReq* q) {
+  q->sched = sched_dev;
+  q->K = K;
+  q->has_watch = 1;
+  q->watch = watch_dev;
+  q->n_watch = n_watch;
+  q->B_watch = B_watch;
+}
+
 // A direct run: validate, then enqueue on the caller's stream, in the weight type the request names.
 int run_direct(const RunReq& q) {
   RunPlan p;
@@ -6545,6 +6782,22 @@ int yuma_run_sched(int variant, const yuma_params_t* params_dev, int N, int E, i
   return run_direct(q);
 }
 
+int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                   const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                   const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                   float* B_watch, void* workspace, size_t workspace_bytes, int chunk_epochs,
+                   const yuma_run_options_t* opts, void* stream, float* phase_ms) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_watch(sched_dev, K, watch_dev, n_watch, B_watch, &q);
+  return run_direct(q);
+}
+
+int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags) {
+  return watch_native(variant, N, E, V, M, n_watch, flags) ? 1 : 0;
+}
+
 int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma_outputs_t* out, int flags) {
   return sched_native(variant, N, E, K, V, M, out, flags) ? 1 : 0;
 }
@@ -6623,6 +6876,18 @@ int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_
            chunk_epochs, nullptr, nullptr};
   if (const int err = read_opts(opts, &q)) return err;
   if (const int err = read_sched(sched_dev, K, &q)) return err;
+  return graph_create_impl(graph, q);
+}
+
+int yuma_graph_create_watch(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
+                            int K, int V, int M, const float* W, const float* S, const int32_t* sched_dev,
+                            const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                            const int32_t* watch_dev, int n_watch, float* B_watch, void* workspace,
+                            size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_watch(sched_dev, K, watch_dev, n_watch, B_watch, &q);
   return graph_create_impl(graph, q);
 }
 

@@ -51,6 +51,9 @@ EXPORTED_SYMBOLS = (
     "yuma_run_sched",
     "yuma_sched_native",
     "yuma_graph_create_sched",
+    "yuma_run_watch",
+    "yuma_watch_native",
+    "yuma_graph_create_watch",
     "yuma_epoch",
     "yuma_synth_weights",
     "yuma_shard_stage",
@@ -217,6 +220,16 @@ def load_library(path: str | None = None):
             lib.yuma_graph_create_sched.argtypes = [ctypes.POINTER(vp), i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
                                                     vp, vp, vp, sz, i32, vp]
             lib.yuma_graph_create_sched.restype = i32
+        # watched columns: yuma_run_sched's arguments, the list, its length and B_watch after `out`
+        if hasattr(lib, "yuma_run_watch"):  # (A/B libraries of older sources lack them)
+            a = lib.yuma_run_sched.argtypes
+            lib.yuma_run_watch.argtypes = a[:13] + [vp, i32, vp] + a[13:]
+            lib.yuma_run_watch.restype = i32
+            a = lib.yuma_graph_create_sched.argtypes
+            lib.yuma_graph_create_watch.argtypes = a[:14] + [vp, i32, vp] + a[14:]
+            lib.yuma_graph_create_watch.restype = i32
+            lib.yuma_watch_native.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+            lib.yuma_watch_native.restype = i32
         lib.yuma_graph_launch.argtypes = [vp, vp]
         lib.yuma_graph_launch.restype = i32
         lib.yuma_graph_nodes.argtypes = [vp]
@@ -479,7 +492,9 @@ class RunResult:
     B_final: torch.Tensor             # [N, V, M]
     B_hist: torch.Tensor | None       # [E, N, V, M]; [len(hist_epochs), N, V, M] under a history stride
     extra: dict
-    hist_epochs: tuple[int, ...] | None = None  # the epoch each B_hist slice holds (None: no history)
+    hist_epochs: tuple[int, ...] | None = None  # the epoch each B_hist / B_watch slice holds (None: neither)
+    B_watch: torch.Tensor | None = None         # [len(hist_epochs), N, V, len(watch_cols)] (run(watch=))
+    watch_cols: tuple[int, ...] | None = None   # the miner column of each B_watch column
 
 
 def _as_dev(x: torch.Tensor, dev) -> torch.Tensor:
@@ -534,6 +549,34 @@ def sched_native(variant: int, N: int, E: int, K: int, V: int, M: int, want_hist
     flags = ((RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
              | (RUN_HIST_BF16 if hist_bf16 else 0))
     return bool(load_library().yuma_sched_native(variant, N, E, K, V, M, ctypes.addressof(outs), flags))
+
+
+def watch_native(variant: int, N: int, E: int, V: int, M: int, n_watch: int, *, shared_inputs: bool = False,
+                 w_u16: bool = False) -> bool:
+    """Whether `run(..., watch=)` with these arguments has the engine write the
+    watched history itself (yuma_watch_native; needs the library, not a GPU):
+    Yuma 3 / Yuma 4, any V, any M and alignment, no shared inputs. Otherwise
+    `run` writes an fp32 history and gathers the columns, and RunGraph refuses."""
+    flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+    return bool(load_library().yuma_watch_native(variant, N, E, V, M, n_watch, flags))
+
+
+def _watch_host(watch, M: int | None, name: str = "watch") -> torch.Tensor:
+    """The watch list as a CPU int64 tensor, validated on the host: integers,
+    one dimension, at least one column, every entry in [0, M) (M None: not
+    negative). ValueError otherwise."""
+    t = watch if isinstance(watch, torch.Tensor) else torch.as_tensor(np.asarray(watch))
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"{name} must hold integer miner indices, not {t.dtype}")
+    if t.dim() != 1 or t.numel() < 1:
+        raise ValueError(f"{name} must be a non-empty one-dimensional list of miner indices, not shape "
+                         f"{tuple(t.shape)}")
+    h = t.detach().to(device="cpu", dtype=torch.int64)
+    lo, hi = int(h.min()), int(h.max())
+    if lo < 0 or (M is not None and hi >= M):
+        raise ValueError(f"{name} entries must lie in [0, M{'' if M is None else '=' + str(M)}): found "
+                         f"{lo if lo < 0 else hi}")
+    return h
 
 
 def _int_view(t: torch.Tensor) -> torch.Tensor:
@@ -659,11 +702,12 @@ def _vector_form(W: torch.Tensor, w_u16: bool, B_init, Wprev_init, o: dict, hist
 
 
 def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_inputs, hist_stride, hist_first,
-                hist_dtype, sched):
+                hist_dtype, sched, watch=None):
     """run's argument checks, in the order run has always raised them: the
     history type and the schedule before anything touches a GPU, the rest
-    behind device(). Returns (dev, N, E, K, sched_host, h_epochs); K and
-    sched_host are None without a schedule."""
+    behind device(). Returns (dev, N, E, K, sched_host, h_epochs, watch_host);
+    K and sched_host are None without a schedule, watch_host without a watch
+    list."""
     if hist_dtype not in (None, torch.float32, torch.bfloat16):
         raise ValueError(f"hist_dtype={hist_dtype} must be None, torch.float32 or torch.bfloat16")
     if hist_dtype == torch.bfloat16 and single_call:
@@ -679,6 +723,7 @@ def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_in
                 raise ValueError(f"out[{name!r}] holds {t.shape[0]} epochs, the schedule {E}")
         if S.shape != (K, Nw, V):
             raise ValueError(f"S shape {tuple(S.shape)} is not [K={K}, N={Nw}, V={V}] of W {tuple(W.shape)}")
+    watch_host = None if watch is None else _watch_host(watch, M)  # before anything touches a GPU
     check_limits(V, M)
     dev = device()
     if sched is None and S.shape != (E, Nw, V):
@@ -698,7 +743,7 @@ def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_in
             raise ValueError("single_call does not take shared inputs")
     elif len(params) != N:
         raise ValueError("one parameter record per scenario is required")
-    return dev, N, E, K, sched_host, h_epochs
+    return dev, N, E, K, sched_host, h_epochs, watch_host
 
 
 def _alloc_history(o: dict, dev, shape, *, want_hist: bool, h_bf16: bool, native_ok) -> bool:
@@ -727,11 +772,17 @@ _OUT_SHAPES = {
 }
 
 
-def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms) -> None:
-    """The run's one launch: yuma_run_opts, or yuma_run_sched under a native
-    schedule; with `capture`, their yuma_graph_create_* twins, the handle
-    appended to it. head: variant, params, N, E; tail: V, M ... chunk_epochs."""
-    if sched_dev is None:
+def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None) -> None:
+    """The run's one launch: yuma_run_opts, yuma_run_sched under a native
+    schedule, or yuma_run_watch with a native watch list (watch: the int32
+    device list, B_watch and the buffer whose address the engine gets); with `capture`, their yuma_graph_create_* twins,
+    the handle appended to it. head: variant, params, N, E; tail: V, M ...
+    chunk_epochs."""
+    if watch is not None:  # yuma_run_sched's arguments (no schedule: NULL, K = 0), the list after `out`
+        run_fn, graph_fn = lib.yuma_run_watch, lib.yuma_graph_create_watch
+        args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
+                + (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr()) + tail[7:])
+    elif sched_dev is None:
         run_fn, graph_fn, args = lib.yuma_run_opts, lib.yuma_graph_create_opts, head + tail
     else:  # E and K in place of E, the schedule after S
         run_fn, graph_fn = lib.yuma_run_sched, lib.yuma_graph_create_sched
@@ -756,7 +807,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         workspace: torch.Tensor | None = None, out: dict | None = None,
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
-        hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None) -> RunResult:
+        hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None,
+        watch=None) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -789,13 +841,37 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     int32 device tensor a captured run re-reads at every replay); elsewhere,
     and under single_call, the inputs are expanded on the device and the dense
     path runs (extra["sched_path"] == "expanded"; a captured run raises
+    EngineError instead).
+    watch: a non-empty sequence or integer tensor of miner indices (duplicates
+    and any order allowed; validated on the host, ValueError): the result's
+    B_watch [n_hist, N, V, len(watch)] is the fp32 bond history of those
+    columns alone, bit-equal to B_hist[..., watch] of the run without a watch
+    list, at the epochs hist_stride / hist_first select (RunResult.hist_epochs;
+    watch_cols names the columns). want_hist=False with watch= is the normal
+    call: the main run then takes the history-less scans; both together give
+    both histories. Where watch_native holds the engine writes B_watch itself
+    (yuma_run_watch, extra["watch_path"] == "native"; extra["watch"] is the
+    int32 device list a captured run re-reads at every replay -- a caller's own
+    contiguous int32 device tensor is used as it is); elsewhere (Yuma 0 / 1 /
+    2, shared inputs, single_call) the run writes an fp32 history, the columns
+    are gathered from it on the device and the dense history is dropped unless
+    asked for (extra["watch_path"] == "dense"; a captured run raises
     EngineError instead)."""
     h_bf16 = hist_dtype == torch.bfloat16
-    dev, N, E, K, sched_host, h_epochs = _check_args(
+    dev, N, E, K, sched_host, h_epochs, watch_host = _check_args(
         params, W, S, B_init, Wprev_init, out, single_call=single_call, shared_inputs=shared_inputs,
-        hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched)
+        hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched, watch=watch)
     V, M = W.shape[2:]
     lib = load_library()
+    # a watch list the engine does not take natively rides on an fp32 history of the run's own
+    watch_dense = watch_host is not None and (
+        single_call or not watch_native(variant, N, E, V, M, watch_host.numel(), shared_inputs=shared_inputs))
+    if watch_dense and capture is not None:
+        raise EngineError("a captured run cannot gather a dense history: watch= needs "
+                          "watch_native(variant, N, E, V, M, n_watch)")
+    hist_asked = want_hist or (out or {}).get("B_hist") is not None
+    if watch_dense and not hist_asked:
+        want_hist, hist_dtype, h_bf16 = True, None, False  # (dropped again below)
     # uint16 weights stay 16-bit on the device where the engine reads them
     # natively (u16_native); anywhere else they are widened like any dtype
     w_u16 = False
@@ -855,6 +931,16 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                 raise EngineError("a captured run cannot expand its inputs: sched= needs "
                                   "sched_native(variant, N, E, K, V, M, ...) and vector-aligned buffers")
             W, S = _take_slices(W, sched_host.to(dev)), _take_slices(S, sched_host.to(dev))
+    watch_arg = None
+    if watch_host is not None and not watch_dense:
+        if (isinstance(watch, torch.Tensor) and watch.device == dev and watch.dtype == torch.int32
+                and watch.is_contiguous()):
+            watch_dev = watch  # the caller's tensor: a captured run follows its in-place updates
+        else:
+            watch_dev = watch_host.to(device=dev, dtype=torch.int32)
+        b_watch = torch.empty((len(h_epochs), N, V, watch_host.numel()), dtype=torch.float32, device=dev)
+        # (no stored epoch: nothing is written, but the engine refuses a null B_watch)
+        watch_arg = (watch_dev, b_watch, b_watch if h_epochs else torch.empty(1, dtype=torch.float32, device=dev))
     full = o.get("Tv") is not None
     if sched_dev is not None:
         nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
@@ -877,7 +963,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         _launch(lib, dev, (variant, prm.data_ptr(), N, E), K, sched_dev,
                 (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
                  workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
-                capture=capture, phase_ms=phase_ms)
+                capture=capture, phase_ms=phase_ms, watch=watch_arg)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -889,7 +975,18 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     hist = o.get("B_hist")
     if h_bf16 and hist is not None and not hist_native:  # the fp32 history, rounded to nearest even
         hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)
-    return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs)
+    if watch_host is None:
+        return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs)
+    keep["watch_path"] = "dense" if watch_dense else "native"
+    if watch_dense:  # the columns of the run's fp32 history (o: before any bfloat16 conversion)
+        b_watch = o["B_hist"].index_select(3, watch_host.to(dev)).contiguous()
+        keep["watch"] = None
+        if not hist_asked:
+            hist = None
+    else:
+        keep["watch"] = watch_dev
+    return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, h_epochs, b_watch,
+                     tuple(int(c) for c in watch_host.tolist()))
 
 
 class RunGraph:

@@ -93,7 +93,7 @@ def _reward_key(config: YumaConfig) -> tuple:
 
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                     want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None,
-                    dedup_inputs: bool = False):
+                    dedup_inputs: bool = False, bonds_columns=None):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
@@ -110,17 +110,33 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     distinct (W, S) slices and a schedule (engine.dedup_slices, engine.run's
     sched): the cases hold a few matrices for tens of epochs each, so the
     engine stores and analyses each distinct slice once. Every returned
-    dividend, bond and incentive is bit-identical to the default."""
+    dividend, bond and incentive is bit-identical to the default.
+    bonds_columns: a non-empty sequence of miner indices, valid for every run
+    of the call (ValueError names the first run whose M is too small): each
+    run's bonds list then holds [V, len(bonds_columns)] tensors, the default's
+    `[:, bonds_columns]` bit for bit -- the servers a chart plots. The engine
+    then keeps no [V, M] history (engine.run's watch). Combines with
+    bonds_every, dedup_inputs and bonds_dtype (bfloat16: the small fp32
+    watched history, converted)."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
     if bonds_dtype not in (None, torch.float32, torch.bfloat16):
         raise ValueError(f"bonds_dtype={bonds_dtype} must be None, torch.float32 or torch.bfloat16")
+    if bonds_columns is not None:  # validated on the host, before anything touches a GPU
+        cols = engine._watch_host(bonds_columns, None, "bonds_columns")
+        bonds_columns = tuple(int(c) for c in cols.tolist())
+        for k, r in enumerate(runs):
+            M = r.case.packed_inputs()[0].shape[-1]
+            if max(bonds_columns) >= M:
+                raise ValueError(f"bonds_columns: index {max(bonds_columns)} is outside run {k} "
+                                 f"('{r.case.name}', {r.yuma_version}), which has M={M} miners")
     # the result lists are thousands of fresh containers (the sheet: 1512
     # dividend lists): the cyclic collector would sweep the process's whole
     # heap several times while they are built; they hold no cycles
     with _no_cyclic_gc():
         return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every),
-                                bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs))
+                                bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs),
+                                bonds_columns=bonds_columns)
 
 
 @contextmanager
@@ -177,7 +193,8 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
-                     totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False):
+                     totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False,
+                     bonds_columns=None):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -220,12 +237,17 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
         sched = None
         if dedup_inputs:  # the group's distinct joint slices and the schedule over them
             W, S, sched = engine.dedup_slices(W, S)
-        launched.append((E, V, idx, S_host, engine.run(variant, params, W, S, want_hist=want_bonds,
-                                                              hist_stride=bonds_every, sched=sched,
-                                                              hist_dtype=bonds_dtype if want_bonds else None)))
+        watch = bonds_columns if want_bonds else None  # the watched columns in place of the [V, M] history
+        launched.append((E, V, idx, S_host, engine.run(
+            variant, params, W, S, want_hist=want_bonds and watch is None, hist_stride=bonds_every, sched=sched,
+            hist_dtype=bonds_dtype if want_bonds and watch is None else None, watch=watch)))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
-        hist = res.B_hist.cpu() if want_bonds else None
+        hist = None
+        if want_bonds and bonds_columns is not None:
+            hist = res.B_watch.to(torch.bfloat16).cpu() if bonds_dtype == torch.bfloat16 else res.B_watch.cpu()
+        elif want_bonds:
+            hist = res.B_hist.cpu()
         inc = res.I.cpu() if want_incentives else None
         # the dividend ratio of the whole group in one pass of the same
         # elementwise ops when its runs share the reward scalars (the sheet)
