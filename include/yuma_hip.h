@@ -356,6 +356,65 @@ int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, i
                    int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms);
 int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags);
 
+/* ------------------------------------------------------------------------
+ * Which bond scan a call reaches. Host only, needs no GPU and makes no HIP
+ * call: the engine's own choice (the function its runs call before they launch
+ * the scan), reported for the first chunk of yuma_run_opts / yuma_run_sched
+ * (has_sched != 0) with these arguments, or for stage 4 of yuma_shard_stage
+ * (shard_stage != 0: no options, no schedule). Of `out` it reads only which
+ * pointers are non-NULL. vector_form is given, not derived from buffers: 1
+ * for M % 4 == 0 and aligned matrices (see YUMA_RUN_W_U16), 0 for the scalar
+ * form. Returns YUMA_OK and fills *plan, or the code the run returns for
+ * sizes, options, or a schedule / YUMA_RUN_W_U16 / YUMA_RUN_HIST_BF16 that is
+ * not native or not in vector form. The kernels and their flags are described
+ * in DESIGN.md section 2.0.
+ * ---------------------------------------------------------------------- */
+enum { /* yuma_scan_plan_t.form: the kernel */
+  YUMA_SCAN_TILE = 0,     /* k_bonds: a block owns the columns of a 64-miner tile    */
+  YUMA_SCAN_STRIP = 1,    /* k_bonds_cn: a block owns a 16-miner strip               */
+  YUMA_SCAN_RUST_BIG = 2, /* k_rust_big_ema + k_rust_big_norm, one pair per epoch    */
+  YUMA_SCAN_ELEM = 3,     /* k_bonds_elem                                            */
+  YUMA_SCAN_GRP = 4       /* k_bonds_grp: the shared-input sweep scan                */
+};
+enum { /* yuma_scan_plan_t.shape: k_bonds_elem's block shape */
+  YUMA_ELEM_NONE = 0,      /* (another kernel)                                       */
+  YUMA_ELEM_WIDE = 1,      /* 512 threads x 1024 miners, 2 rows, the history         */
+  YUMA_ELEM_TILE_HIST = 2, /* 256 threads on 64-miner tiles, 2 rows, the history     */
+  YUMA_ELEM_TILE = 3,      /* ... without the history                                */
+  YUMA_ELEM_FLAT1 = 4,     /* 256 threads x 256 miners, 1 row                        */
+  YUMA_ELEM_FLAT2 = 5      /* ... 2 rows                                             */
+};
+enum { YUMA_SCAN_HIST_NONE = 0, YUMA_SCAN_HIST_FP32 = 1, YUMA_SCAN_HIST_BF16 = 2 };
+enum { /* yuma_scan_plan_t.dpl: layout of the dividend partials */
+  YUMA_DP_TV = 0, /* [slice][tile][V]             */
+  YUMA_DP_VQ = 1, /* [slice][V][quad]             */
+  YUMA_DP_QTE = 2 /* [scenario][quad][V][epoch]   */
+};
+typedef struct {
+  long long grid;      /* blocks of the launch                                     */
+  int32_t variant;     /* as given                                                 */
+  int32_t vector_form; /* as given                                                 */
+  int32_t w_u16;       /* W element type: uint16 (YUMA_RUN_W_U16)                  */
+  int32_t form;        /* YUMA_SCAN_*                                              */
+  int32_t shape;       /* YUMA_ELEM_*                                              */
+  int32_t rows;        /* rows per lane (k_bonds: rows per thread)                 */
+  int32_t rq;          /* RQ: divides by k_rowsum's screened reciprocals           */
+  int32_t hs;          /* HS: a strided history                                    */
+  int32_t hist;        /* a history is written                                     */
+  int32_t nt;          /* NT: non-temporal history stores (k_bonds_elem)           */
+  int32_t hist_bf16;   /* HT: the history's elements are bfloat16                  */
+  int32_t sc;          /* SC: under an input schedule                              */
+  int32_t rowblocks;   /* row blocks per scenario and column block                 */
+  int32_t cblocks;     /* column blocks                                            */
+  int32_t block;       /* threads per block                                        */
+  int32_t ptiles;      /* dividend partials per slice and validator                */
+  int32_t dpl;         /* YUMA_DP_*                                                */
+  int32_t rc;          /* k_bonds: 0 256 threads x 1 row, 1 256 x 4, 2 256 x 16, 3 1024 x 16 */
+} yuma_scan_plan_t;    /* 80 bytes */
+int yuma_scan_plan(int variant, int N, int E, int V, int M, const yuma_outputs_t* out,
+                   const yuma_run_options_t* opts, int vector_form, int has_sched, int shard_stage,
+                   yuma_scan_plan_t* plan);
+
 /* hipGraph form of yuma_run: the whole multi-epoch run (every phase of every
  * chunk, no host work between them) captured once into a HIP graph and
  * replayed with one hipGraphLaunch. The arguments are those of yuma_run and

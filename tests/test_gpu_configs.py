@@ -72,7 +72,7 @@ def _shared_vs_replicated_and_oracle(ids: list[int], E: int, oracle_ids: list[in
     """The launch `bench.py --config c3` times: every scenario reads ONE W/S
     trajectory (shared_inputs, yuma_run_ex YUMA_RUN_SHARED_INPUTS), no bond
     history. At 256 x 4096 that is the shared-input bond scan
-    (launch_bonds_elem: k_bonds_grp<YUMA4, K=4, R=2, P=2>, four scenarios per
+    (plan_scan: k_bonds_grp<YUMA4, K=4, R=2, P=2>, four scenarios per
     block over one 32-row x 64-miner W tile), the row sums once per input
     epoch and the consensus / quantisation input / rank once per consensus
     class (k_classes). C, Dn, I and B_final must be

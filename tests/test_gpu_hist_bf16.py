@@ -77,23 +77,27 @@ class Case:
     kind: str = "run"  # run | sweep | u16 | graph
     reset: bool = False  # Yuma 3, reset_mode ALWAYS at RESET_EPOCH
     strided: bool = False  # also run under STRIDES
+    # the bond scan the case is there to reach with a dense bfloat16 history, as tests/test_scan_plan_host.py
+    # spells a plan (reached()); checked there without a GPU. FALLBACK cases are refused a native history.
+    reach: str = ""
 
 
 NATIVE = [
     # k_bonds_elem 512 x 1024, second column block 4 miners wide
-    Case("wide-yuma3", Y3, 2, 70, 1028, strided=True),
-    Case("wide-yuma4-liquid", Y4, 2, 70, 1028, liquid=True, strided=True),
+    Case("wide-yuma3", Y3, 2, 70, 1028, strided=True, reach="wide+bf16"),
+    Case("wide-yuma4-liquid", Y4, 2, 70, 1028, liquid=True, strided=True, reach="wide+bf16"),
     # k_bonds_elem R = 2 on 64-miner tiles
-    Case("tile-yuma3", Y3, 2, 70, 260, strided=True),
-    Case("tile-yuma4", Y4, 2, 70, 260, strided=True),
+    Case("tile-yuma3", Y3, 2, 70, 260, strided=True, reach="tile_hist+bf16"),
+    Case("tile-yuma4", Y4, 2, 70, 260, strided=True, reach="tile_hist+bf16"),
     # one and two row blocks' worth of validators below a full block, a half-filled last tile
-    Case("small16-yuma3", Y3, 2, 16, 132), Case("small16-yuma4", Y4, 2, 16, 132),
-    Case("small40-yuma3", Y3, 2, 40, 132), Case("small40-yuma4", Y4, 2, 40, 132),
+    Case("small16-yuma3", Y3, 2, 16, 132, reach="tile_hist+bf16"), Case("small16-yuma4", Y4, 2, 16, 132, reach="tile_hist+bf16"),
+    Case("small40-yuma3", Y3, 2, 40, 132, reach="tile_hist+bf16"), Case("small40-yuma4", Y4, 2, 40, 132, reach="tile_hist+bf16"),
     # the same kernel above 1024 validators
-    Case("bigv-yuma3", Y3, 1, 1100, 96),
-    Case("u16-yuma3", Y3, 2, 70, 1028, kind="u16"),
-    Case("reset-wide-yuma3", Y3, 2, 70, 1028, reset=True), Case("reset-tile-yuma3", Y3, 2, 70, 260, reset=True),
-    Case("graph-yuma3", Y3, 2, 64, 512, kind="graph"),
+    Case("bigv-yuma3", Y3, 1, 1100, 96, reach="tile_hist+bf16"),
+    Case("u16-yuma3", Y3, 2, 70, 1028, kind="u16", reach="wide+bf16+u16"),
+    Case("reset-wide-yuma3", Y3, 2, 70, 1028, reset=True, reach="wide+bf16"),
+    Case("reset-tile-yuma3", Y3, 2, 70, 260, reset=True, reach="tile_hist+bf16"),
+    Case("graph-yuma3", Y3, 2, 64, 512, kind="graph", reach="tile_hist+bf16"),
 ]
 FALLBACK = [
     Case("yuma1", Y1, 2, 70, 260),
@@ -101,6 +105,17 @@ FALLBACK = [
     Case("scalar-yuma3", Y3, 1, 70, 262),
     Case("sweep-yuma3", Y3, 6, 70, 260, kind="sweep"),
 ]
+
+
+def plan_args(case, strided=False):
+    """engine.scan_plan's arguments for a case's native bfloat16 runs (strided: stride 3 from epoch 2)."""
+    return (case.variant, case.N, E, case.V, case.M), dict(
+        want_hist=True, hist_bf16=True, hist_stride=3 if strided else 1, shared_inputs=case.kind == "sweep",
+        w_u16=case.kind == "u16")
+
+
+# every k_bonds_elem shape the native list reaches, dense and (strided cases) with +hs
+COVERED = {"wide", "tile_hist"}
 
 
 def configs(case):

@@ -71,6 +71,9 @@ class Case:
     liquid: bool = False
     kind: str = "run"  # run | sweep | u16 | graph
     reset: bool = False  # Yuma 3, reset_mode ALWAYS at RESET_EPOCH
+    # the bond scan the case is there to reach under a stride, as tests/test_scan_plan_host.py spells a plan
+    # (reached()): kernel or k_bonds_elem shape, then +rq +hs ... and /scalar; checked there without a GPU
+    reach: str = ""
 
 
 def _cases():
@@ -78,25 +81,42 @@ def _cases():
     # k_bonds RC_256_1 / RC_256_4 (column-normalised, <= 64 validators), the
     # 64-miner-tile history scan for Yuma 3 / 4
     for V in (16, 40):
-        c += [Case(f"small{V}-{NAME[v]}", v, 2, V, 132) for v in ALL5]
+        c += [Case(f"small{V}-{NAME[v]}", v, 2, V, 132,
+                   reach="tile_hist+hs" if v in (Y3, Y4) else f"k_bonds<256,{1 if V == 16 else 4}>+hs") for v in ALL5]
     # k_bonds_cn at 1, 2, 4, 8 rows per lane, a half-filled last strip
-    c += [Case(f"strip-V{V}", RUST, 2, V, 72) for V in (100, 200, 384, 1000)]
+    c += [Case(f"strip-V{V}", RUST, 2, V, 72, reach=f"k_bonds_cn<{rows}>+rq+hs")
+          for V, rows in ((100, 1), (200, 2), (384, 4), (1000, 8))]
     # k_bonds_elem 512 x 1024, second column block 4 miners wide
-    c += [Case(f"widehist-{NAME[v]}", v, 2, 70, 1028, liquid=v == Y4) for v in (Y1, Y2, Y3, Y4)]
+    c += [Case(f"widehist-{NAME[v]}", v, 2, 70, 1028, liquid=v == Y4,
+               reach="wide+rq+hs" if v in (Y1, Y2) else "wide+hs") for v in (Y1, Y2, Y3, Y4)]
     # k_bonds_elem R = 2 on 64-miner tiles
-    c += [Case(f"tilehist-{NAME[v]}", v, 2, 70, 260) for v in (Y1, Y2, Y3, Y4)]
+    c += [Case(f"tilehist-{NAME[v]}", v, 2, 70, 260, reach="tile_hist+hs") for v in (Y1, Y2, Y3, Y4)]
     # the VEC = false forms (M % 4 != 0): k_bonds, and the scalar one-row scan's history
-    c += [Case(f"scalar-hist-{NAME[v]}", v, 1, 70, 262) for v in ALL5]
+    c += [Case(f"scalar-hist-{NAME[v]}", v, 1, 70, 262,
+               reach="k_bonds<256,16>+hs/scalar" if v == RUST else "flat1+hs/scalar") for v in ALL5]
     # k_bonds_grp: one full group of 4 scenarios and one of 2
-    c += [Case(f"sweep-hist-{NAME[v]}", v, 6, 70, 260, kind="sweep") for v in (Y3, Y4)]
+    c += [Case(f"sweep-hist-{NAME[v]}", v, 6, 70, 260, kind="sweep", reach="k_bonds_grp+rq+hs+hist") for v in (Y3, Y4)]
     # k_rust_big_ema / k_rust_big_norm, the element-wise scan above 1024 validators
-    c += [Case(f"bigv-{NAME[v]}", v, 1, 1100, 96) for v in (RUST, Y1, Y2, Y3)]
+    c += [Case(f"bigv-{NAME[v]}", v, 1, 1100, 96, reach="k_rust_big+hs" if v == RUST else "tile_hist+hs")
+          for v in (RUST, Y1, Y2, Y3)]
     # native uint16 W
-    c += [Case("u16-yuma3", Y3, 2, 70, 1028, kind="u16")]
-    c += [Case("graph-yuma3", Y3, 2, 64, 512, kind="graph")]
+    c += [Case("u16-yuma3", Y3, 2, 70, 1028, kind="u16", reach="wide+hs+u16")]
+    c += [Case("graph-yuma3", Y3, 2, 64, 512, kind="graph", reach="tile_hist+hs")]
     # a reset between stored epochs, on the wide and the tile scan
-    c += [Case("reset-wide-yuma3", Y3, 2, 70, 1028, reset=True), Case("reset-tile-yuma3", Y3, 2, 70, 260, reset=True)]
+    c += [Case("reset-wide-yuma3", Y3, 2, 70, 1028, reset=True, reach="wide+hs"),
+          Case("reset-tile-yuma3", Y3, 2, 70, 260, reset=True, reach="tile_hist+hs")]
     return c
+
+
+def plan_args(case):
+    """engine.scan_plan's arguments for a case's strided runs (stride 3 from epoch 2)."""
+    return (case.variant, case.N, E, case.V, case.M), dict(
+        want_hist=True, hist_stride=3, shared_inputs=case.kind == "sweep", w_u16=case.kind == "u16")
+
+
+# every (kernel or shape, strip rows) the list reaches: a case taken out or moved must leave this as it is
+COVERED = {"k_bonds<256,1>", "k_bonds<256,4>", "k_bonds<256,16>", "k_bonds_cn<1>", "k_bonds_cn<2>", "k_bonds_cn<4>",
+           "k_bonds_cn<8>", "k_rust_big", "k_bonds_grp", "wide", "tile_hist", "flat1"}
 
 
 CASES = _cases()

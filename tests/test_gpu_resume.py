@@ -3,7 +3,7 @@ Yuma 2, previous normalised weights Wprev_init [N,V,M] on every bond scan and
 rank form of the multi-epoch run (engine.run, engine.RunGraph,
 wide.run_wide_local).
 
-For each launch shape of launch_bonds* / launch_rank (CASES names the kernel a
+For each launch shape of plan_scan / launch_rank (CASES names the kernel a
 shape is meant to reach):
 
   * bitwise split: run(E) == run(E1) followed by run(E - E1, B_init = B_final
@@ -69,51 +69,84 @@ class Case:
     reset: str | None = None  # "always" (at whole-run epoch E1) | "if_zero_c" (at E1 + 1)
     scenarios: tuple = ()     # the scenarios compared with the oracle (default: all)
     device_inputs: bool = False
+    # the bond scan the case is there to reach, as tests/test_scan_plan_host.py spells a plan (reached()):
+    # kernel or k_bonds_elem shape, then +rq +hs +bf16 +sc +u16 and /scalar; checked there without a GPU
+    reach: str = ""
 
 
 def _cases():
     c = []
     # k_bonds RC_256_1 / RC_256_4 (column-normalised, <= 64 validators), the
     # 64-miner-tile history scan for Yuma 3 / 4; Yuma 2: k_rank_s without column sums
-    for V in (16, 40):
-        c += [Case(f"small{V}-{NAME[v]}", v, 2, V, 132, True) for v in ALL5]
+    for V, rows in ((16, 1), (40, 4)):
+        c += [Case(f"small{V}-{NAME[v]}", v, 2, V, 132, True,
+                   reach="tile_hist" if v in (Y3, Y4) else f"k_bonds<256,{rows}>") for v in ALL5]
     # k_bonds_cn at 1, 2, 4, 8 rows per lane, a half-filled last strip (72 = 4 * 16 + 8)
-    c += [Case(f"strip-V{V}", RUST, 2, V, 72, True) for V in (100, 200, 384, 1000)]
+    c += [Case(f"strip-V{V}", RUST, 2, V, 72, True, reach=f"k_bonds_cn<{rows}>+rq")
+          for V, rows in ((100, 1), (200, 2), (384, 4), (1000, 8))]
     # k_bonds_elem 512 x 1024 (Yuma 1 / 2 on the screened reciprocal, Yuma 3 / 4
     # without), second column block 4 miners wide; Yuma 2: k_rank_sw with column sums
-    c += [Case(f"widehist-{NAME[v]}", v, 2, 70, 1028, True, liquid=v == Y4) for v in (Y1, Y2, Y3, Y4)]
+    c += [Case(f"widehist-{NAME[v]}", v, 2, 70, 1028, True, liquid=v == Y4, reach="wide+rq" if v in (Y1, Y2) else "wide")
+          for v in (Y1, Y2, Y3, Y4)]
     # k_bonds_elem R = 2 on 64-miner tiles (DP_TV)
-    c += [Case(f"tilehist-{NAME[v]}", v, 2, 70, 260, True) for v in (Y1, Y2, Y3, Y4)]
+    c += [Case(f"tilehist-{NAME[v]}", v, 2, 70, 260, True, reach="tile_hist") for v in (Y1, Y2, Y3, Y4)]
     # the one-row history-less scan, epoch-minor partials + k_dte_sum
-    c += [Case(f"nohist1-{NAME[v]}", v, 2, 70, 260, False, liquid=v == Y4) for v in (Y1, Y2, Y3, Y4)]
+    c += [Case(f"nohist1-{NAME[v]}", v, 2, 70, 260, False, liquid=v == Y4, reach="flat1+rq") for v in (Y1, Y2, Y3, Y4)]
     # the two-row history-less scan: blocks_r2 = 32 * 8 * 16 = 4096 (Yuma 3; Yuma 1
     # at 64 validators forms no column sums and takes k_bonds RC_256_4 on 2048
     # blocks, so a 72-validator Yuma 1 case, 29 * 9 * 16 = 4176, reaches the scan)
-    c += [Case("nohist2-yuma3", Y3, 32, 64, 4096, False, scenarios=(0, 17, 31), device_inputs=True),
-          Case("nohist2-yuma1", Y1, 32, 64, 4096, False, scenarios=(0, 17, 31), device_inputs=True),
-          Case("nohist2-yuma1-V72", Y1, 29, 72, 4096, False, scenarios=(0, 28), device_inputs=True)]
+    c += [Case("nohist2-yuma3", Y3, 32, 64, 4096, False, scenarios=(0, 17, 31), device_inputs=True, reach="flat2+rq"),
+          Case("nohist2-yuma1", Y1, 32, 64, 4096, False, scenarios=(0, 17, 31), device_inputs=True,
+               reach="k_bonds<256,4>"),
+          Case("nohist2-yuma1-V72", Y1, 29, 72, 4096, False, scenarios=(0, 28), device_inputs=True, reach="flat2+rq")]
     # the VEC = false forms (M % 4 != 0)
     for hist in (True, False):
-        c += [Case(f"scalar-{'hist' if hist else 'nohist'}-{NAME[v]}", v, 1, 70, 262, hist) for v in ALL5]
+        c += [Case(f"scalar-{'hist' if hist else 'nohist'}-{NAME[v]}", v, 1, 70, 262, hist,
+                   reach="k_bonds<256,16>/scalar" if v == RUST else "flat1/scalar") for v in ALL5]
     # B_init 4 bytes into a larger buffer: the run drops to the scalar kernels
-    c += [Case(f"offset-{NAME[v]}", v, 1, 70, 260, True, kind="offset") for v in (Y3, RUST)]
+    c += [Case(f"offset-{NAME[v]}", v, 1, 70, 260, True, kind="offset",
+               reach="k_bonds<256,16>/scalar" if v == RUST else "flat1/scalar") for v in (Y3, RUST)]
     # k_bonds_grp: one full group of 4 scenarios and one of 2, per-scenario B_init
     for hist in (True, False):
-        c += [Case(f"sweep-{'hist' if hist else 'nohist'}-{NAME[v]}", v, 6, 70, 260, hist, kind="sweep")
-              for v in (Y3, Y4)]
+        c += [Case(f"sweep-{'hist' if hist else 'nohist'}-{NAME[v]}", v, 6, 70, 260, hist, kind="sweep",
+                   reach="k_bonds_grp+rq+hist" if hist else "k_bonds_grp+rq") for v in (Y3, Y4)]
     # k_rust_big_ema / k_rust_big_norm, the element-wise scan above 1024
     # validators, the big k_rank_sw with Wprev_init
-    c += [Case(f"bigv-{NAME[v]}", v, 1, 1100, 96, True) for v in (RUST, Y1, Y2, Y3)]
+    c += [Case(f"bigv-{NAME[v]}", v, 1, 1100, 96, True, reach="k_rust_big" if v == RUST else "tile_hist")
+          for v in (RUST, Y1, Y2, Y3)]
     # native uint16 W with an fp32 B_init
-    c += [Case("u16-yuma3", Y3, 2, 70, 1028, True, kind="u16"),
-          Case("u16-yuma4-liquid", Y4, 2, 70, 260, False, liquid=True, kind="u16")]
+    c += [Case("u16-yuma3", Y3, 2, 70, 1028, True, kind="u16", reach="wide+u16"),
+          Case("u16-yuma4-liquid", Y4, 2, 70, 260, False, liquid=True, kind="u16", reach="flat1+rq+u16")]
     # the reset on the caller's state at epoch 0 / at epoch 1 of the second segment
-    c += [Case(f"reset0-{NAME[v]}", v, 2, 70, 1028, True, reset="always") for v in (Y3, Y4)]
-    c += [Case("reset1-yuma3", Y3, 2, 70, 260, False, reset="if_zero_c")]
-    c += [Case(f"graph-{NAME[v]}", v, 2, 64, 512, True, kind="graph") for v in (Y3, Y2)]
-    # the shard stages (k_bonds_cn<..., false> for Yuma 2: no screened reciprocals there)
-    c += [Case(f"shards-{NAME[v]}", v, 1, 130, 520, True, kind="shards") for v in (RUST, Y2, Y3)]
+    c += [Case(f"reset0-{NAME[v]}", v, 2, 70, 1028, True, reset="always", reach="wide") for v in (Y3, Y4)]
+    c += [Case("reset1-yuma3", Y3, 2, 70, 260, False, reset="if_zero_c", reach="flat1+rq")]
+    c += [Case(f"graph-{NAME[v]}", v, 2, 64, 512, True, kind="graph", reach="tile_hist" if v == Y3 else "k_bonds<256,4>")
+          for v in (Y3, Y2)]
+    # the shard stages, three shards of 192, 192 and 136 columns (no screened reciprocals there: k_bonds_cn
+    # without RQ for Yuma 0; Yuma 2 forms its column sums in a stage too and takes the element-wise scan)
+    c += [Case(f"shards-{NAME[v]}", v, 1, 130, 520, True, kind="shards",
+               reach="k_bonds_cn<2>" if v == RUST else "tile_hist") for v in (RUST, Y2, Y3)]
     return c
+
+
+def plan_args(case, shard=None):
+    """engine.scan_plan's arguments for the scan a case's runs launch. The
+    shards cases: stage 4 of the first column shard, and (shard=False) the
+    plain run they are compared with."""
+    shard = case.kind == "shards" if shard is None else shard
+    M = len(wide.column_ranges(case.M, 3)[0]) if shard else case.M
+    return (case.variant, case.N, E, case.V, M), dict(
+        want_hist=case.hist, shared_inputs=case.kind == "sweep", w_u16=case.kind == "u16",
+        vector_form=M % 4 == 0 and case.kind != "offset", shard_stage=shard)
+
+
+# what the plain runs of the shards cases reach (520 miners, with the screened reciprocals)
+SHARDS_RUN_REACH = {"shards-rust": "k_bonds_cn<2>+rq", "shards-yuma2": "tile_hist", "shards-yuma3": "tile_hist"}
+
+
+# every (kernel or shape, strip rows) the list reaches: a case taken out or moved must leave this as it is
+COVERED = {"k_bonds<256,1>", "k_bonds<256,4>", "k_bonds<256,16>", "k_bonds_cn<1>", "k_bonds_cn<2>", "k_bonds_cn<4>",
+           "k_bonds_cn<8>", "k_rust_big", "k_bonds_grp", "wide", "tile_hist", "flat1", "flat2"}
 
 
 CASES = _cases()

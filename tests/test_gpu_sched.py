@@ -5,7 +5,7 @@ have the dense run's bits: torch.equal on Dn, D, C, I, R, Sn, B_hist, B_final
 (and bond_alpha, alpha_ab for liquid scenarios: the engine writes them for
 those only), and extra["sched_path"] == "native".
 
-Scan forms (launch_bonds_elem), named in the test ids:
+Scan forms (plan_scan), named in the test ids:
   tile   (V=70, M=260, N=2) with history: k_bonds_elem R = 2 on 64-miner tiles
   wide   (V=12, M=1024, N=1) with history: the 512 x 1024 scan
   onerow both shapes without history: the one-row history-less form (DP_QTE)
@@ -43,7 +43,19 @@ SCHEDULES = {
     "unreferenced": (4, [0, 1, 1, 2, 2, 2, 0, 0, 1, 2, 0]),  # slice 3 never read
 }
 OOO = SCHEDULES["out-of-order"]
-SHAPES = {"tile": (2, 70, 260), "wide": (1, 12, 1024), "bigv": (1, 1100, 64)}
+SHAPES = {"tile": (2, 70, 260), "wide": (1, 12, 1024), "bigv": (1, 1100, 64), "tworow": (2, 1024, 4096)}
+# the bond scan each (shape, history) of the tests below is there to reach under a schedule, as
+# tests/test_scan_plan_host.py spells a plan (reached()); checked there without a GPU
+REACH = {("tile", True): "tile_hist+sc", ("wide", True): "wide+sc", ("bigv", True): "tile_hist+sc",
+         ("tile", False): "flat1+rq+sc", ("wide", False): "flat1+rq+sc", ("bigv", False): "flat1+rq+sc",
+         ("tworow", False): "flat2+rq+sc"}
+COVERED = {"wide", "tile_hist", "flat1", "flat2"}
+
+
+def plan_args(shape, hist, variant):
+    """engine.scan_plan's arguments for a native schedule run of SHAPES[shape]."""
+    N, V, M = SHAPES[shape]
+    return (variant, N, E, V, M), dict(want_hist=hist, sched=True)
 VARIANTS = {"yuma3": (Y3, False), "yuma4": (Y4, False), "yuma4-liquid": (Y4, True)}
 BASE = ("Dn", "C", "I", "B_final")
 WANT = ("D", "R", "Sn")
@@ -144,7 +156,7 @@ def test_without_history_tworow(vname):
     """The two-row history-less form starts at 4096 blocks of 8 rows x 256
     miners: N = 2, V = 1024, M = 4096 is the smallest grid that has them."""
     variant, liquid = VARIANTS[vname]
-    N, V, M, K = 2, 1024, 4096, 2
+    (N, V, M), K = SHAPES["tworow"], 2
     assert N * ((V + 7) // 8) * ((M + 255) // 256) >= 4096
     key = ("tworow",)
     if key not in _INPUTS:

@@ -17,7 +17,9 @@ PATCHES = {
 }
 
 # k_bonds_grp (c3 sweep scan): one scenario per block, four rows per lane
-PATCHES["grp_k1_r4_w4"] = [("      constexpr int K = kScanGroup, R = 2;", "      constexpr int K = 1, R = 4;")]
+# (the two file-scope constants size the grid in plan_scan as well as the kernel: host dispatch follows the patch)
+PATCHES["grp_k1_r4_w4"] = [("constexpr int kScanGroup = 4;", "constexpr int kScanGroup = 1;"),
+                           ("constexpr int kGrpRows = 2;", "constexpr int kGrpRows = 4;")]
 
 # k_bonds_elem: settle every pre-loop load (bond state, ring prefetch) before the
 # epoch loop, so the waitcnt pass need not drain the ring in the loop
@@ -122,7 +124,7 @@ _CN_CLAMP = [("  for (int k = 0; k < P; ++k)\n    if (A.t0 + k < A.t1) fetch(k, 
               "      fetch(k, min(t + P, A.t1 - 1));  // slot k consumed: refill it\n      if constexpr (!RUST) {\n        cn_wave_sums<NW>(csum, red[par], cq, rr, wave);")]
 PATCHES["cnl_ba"] = _CN_BA
 PATCHES["cnl_clamp"] = _CN_BA + _CN_CLAMP
-_CN_P = "  constexpr int P = R <= 2 ? 4 : (R == 4 ? 2 : 1);  // epochs in flight"
+_CN_P = "constexpr int cn_epochs(int R) { return R <= 2 ? 4 : (R == 4 ? 2 : 1); }"
 PATCHES["cnl_p2"] = [(_CN_P, _CN_P.replace("R <= 2 ? 4 :", "R <= 2 ? 2 :"))]
 PATCHES["cnl_p3"] = [(_CN_P, _CN_P.replace("R <= 2 ? 4 :", "R <= 2 ? 3 :"))]
 PATCHES["cnl_clamp_p3"] = PATCHES["cnl_clamp"] + PATCHES["cnl_p3"]

@@ -2,8 +2,13 @@
 metadata and code bytes; no GPU needed): code size, VGPR / SGPR counts, spills,
 scratch, LDS and kernel-argument size of every k_bonds* / k_rust_big_* kernel
 that both hold, and whether its machine code is byte-identical.
-    python tools/kcompare.py parent/libyuma_hip.so [this/libyuma_hip.so] [-v] [--all]
+    python tools/kcompare.py parent/libyuma_hip.so [this/libyuma_hip.so] [-v] [--all] [--by-code]
 --all compares every kernel of the two code objects, not only the bond scans.
+--by-code pairs the bond scans whose names do not pair (a template parameter
+list that changed shape) by their code: the multisets of (code size, code
+sha1, metadata) of the unpaired kernels of either side must be equal, and any
+kernel left without a partner is printed. With --all, every other kernel is
+still compared under its unchanged name.
 k_bonds_elem's trailing history element type (HT = float, the default) is
 dropped from a name before the two sides are matched, so that a library built
 before that parameter existed pairs with one built after."""
@@ -59,9 +64,28 @@ def key(name):
     return name
 
 
+def pair_by_code(A, B):
+    """The bond scans of A and B that no name pairs, paired by (size, sha1,
+    metadata): the pairs, and the kernels of either side left over."""
+    scan = lambda k: re.search(r"k_bonds|k_rust_big", k)
+    pool = {}
+    for k in sorted(set(B) - set(A)):
+        if scan(k):
+            pool.setdefault(B[k], []).append(k)
+    pairs, left = [], []
+    for k in sorted(set(A) - set(B)):
+        if not scan(k):
+            continue
+        if pool.get(A[k]):
+            pairs.append((k, pool[A[k]].pop(0)))
+        else:
+            left.append(k)
+    return pairs, left, sorted(k for ks in pool.values() for k in ks)
+
+
 def main():
     every = "--all" in sys.argv
-    args = [a for a in sys.argv[1:] if a not in ("-v", "--all")]
+    args = [a for a in sys.argv[1:] if a not in ("-v", "--all", "--by-code")]
     a = kernels(args[0], every)
     b = kernels(args[1] if len(args) > 1 else os.path.join(ROOT, "yuma-simulation_amd", "lib", "libyuma_hip.so"), every)
     A = {key(k): v for k, v in a.items()}
@@ -79,6 +103,20 @@ def main():
     print(f"only in the second ({len(set(B) - set(A))}): {head}")
     for k in sorted(set(B) - set(A)):
         print(" ", k, B[k][0], *B[k][2])
+    if "--by-code" in sys.argv:
+        pairs, la, lb = pair_by_code(A, B)
+        scans = lambda D: sum(1 for k in D if re.search(r"k_bonds|k_rust_big", k))
+        print(f"bond-scan kernels: {scans(A)} in the first library, {scans(B)} in the second; "
+              f"{scans(set(A) & set(B))} under the same name")
+        print(f"bond scans paired by code (byte-identical, equal metadata): {len(pairs)}; "
+              f"without a partner: {len(la)} of the first library, {len(lb)} of the second")
+        for k in la:
+            print("UNPAIRED first ", k, A[k][0], *A[k][2])
+        for k in lb:
+            print("UNPAIRED second", k, B[k][0], *B[k][2])
+        if "-v" in sys.argv:
+            for x, y in pairs:
+                print("  PAIR", x, "\n      ", y)
     if "-v" in sys.argv:
         print(f"in both: {head}")
         for k in both:

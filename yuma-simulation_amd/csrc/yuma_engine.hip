@@ -3246,7 +3246,7 @@ struct BondArgs {
   // hstride = 1, hnext = hslot = t0 (hist_strided() is false, slot == epoch).
   int hstride, hnext, hslot;
   // bfloat16 history (YUMA_RUN_HIST_BF16): B_hist addresses __bf16 elements in
-  // the same [slot][N][V][M] layout. Read on the host only: launch_bonds_elem
+  // the same [slot][N][V][M] layout. Read on the host only: plan_scan
   // picks the HT = __bf16 instantiation of k_bonds_elem from it, no kernel
   // tests it. The word fills what was the record's tail padding (20 pointers
   // and 13 ints left 4 bytes), so sizeof(BondArgs), every other field's offset
@@ -4072,10 +4072,19 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // no fetch waits for it. BondArgs has no room for the two words: the SC
 // instantiations take BondArgsSc, the record with the two appended, and every
 // other instantiation keeps its argument block and its code.
-template <int VARIANT, int R, bool VEC, int P, bool VECI, bool NT = false, int BS = 256, int CB = 64,
-          int DPL = DP_TV, bool RQ = false, typename WT = float, bool HS = false, typename HT = float,
-          bool SC = false>
-__global__ __launch_bounds__(BS, 1) void k_bonds_elem(std::conditional_t<SC, BondArgsSc, BondArgs> A) {
+// SH: the block shape, an ElemShape (R, P, BS, CB as above; VECI: float4
+// incentive / bond_alpha loads; NT: non-temporal history stores; DPL: the
+// dividend-partial layout).
+template <int R_, int P_, bool VECI_, bool NT_, int BS_, int CB_, int DPL_>
+struct ElemShape {
+  static constexpr int R = R_, P = P_, BS = BS_, CB = CB_, DPL = DPL_;
+  static constexpr bool VECI = VECI_, NT = NT_;
+};
+template <int VARIANT, typename SH, bool VEC, bool RQ = false, typename WT = float, bool HS = false,
+          typename HT = float, bool SC = false>
+__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC, BondArgsSc, BondArgs> A) {
+  constexpr int R = SH::R, P = SH::P, BS = SH::BS, CB = SH::CB, DPL = SH::DPL;
+  constexpr bool VECI = SH::VECI, NT = SH::NT;
   static_assert(!SC || (VEC && VARIANT >= YUMA_VARIANT_YUMA3), "input schedules: Yuma 3 / Yuma 4, vector form");
   static_assert(std::is_same_v<HT, float> || (std::is_same_v<HT, __bf16> && NT && VEC && !RQ &&
                                               VARIANT >= YUMA_VARIANT_YUMA3),
@@ -5721,101 +5730,23 @@ void launch_rank(RowCfg, long long nblocks, hipStream_t st, const uint16_t* W, c
             tiles, R, rpart, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
+// ---------------------------------------------------------------------------
+// The bond scan's dispatch. plan_scan chooses: a pure function of a ScanKey,
+// no HIP call, every threshold written once. launch_scan instantiates and
+// launches what the plan names, and nothing else does. DESIGN.md section 2.0
+// is the table; tests/test_scan_plan_host.py holds plan_scan to it through
+// yuma_scan_plan, without a GPU.
+// ---------------------------------------------------------------------------
 // Column-normalised variants (Rust / Yuma1 / Yuma2): one block owns whole
 // columns (single row block). Run outputs of subnets above 64 validators take
 // the strip scan k_bonds_cn (16-miner strips, 8 waves, epochs in flight);
 // small subnets and the full-output epoch (W_b / instantaneous bonds stored)
-// k_bonds on 64-miner tiles. Returns the dividend-partial layout and sets
-// *ptiles to the partials per (slice, validator).
+// k_bonds on 64-miner tiles.
 // The strip scan runs 8 waves per 16-miner strip. Fewer waves with more
 // rows per lane (a cheaper per-epoch column reduction) lose: c2 YumaRust
 // bonds 3.50 -> 5.11 ms with 4 waves, 9.12 with 2 (profiles/r05/ab_cn_waves.txt)
-template <int VARIANT, int R>
-int launch_cn(hipStream_t st, yk::BondArgs& A, int* ptiles) {
-  A.rowblocks = 1;
-  A.cblocks = (A.M + yk::kCnStrip - 1) / yk::kCnStrip;
-  *ptiles = A.cblocks;
-  const long long nblocks = (long long)A.N * A.cblocks;
-  constexpr int P = R <= 2 ? 4 : (R == 4 ? 2 : 1);  // epochs in flight
-  // RQ: k_rowsum's screened reciprocals (run_impl; not the shard stages)
-  with_bool(A.rq4 != nullptr, [&](auto RQ) {
-    with_bool(A.B_hist != nullptr && yk::hist_strided(A), [&](auto HS) {
-      YK_LAUNCH((yk::k_bonds_cn<VARIANT, R, P, 8, decltype(RQ)::value, decltype(HS)::value>), nblocks, 512, st, A);
-    });
-  });
-  return yk::DP_TV;
-}
-template <int VARIANT>
-int launch_cn_rows(hipStream_t st, yk::BondArgs& A, int* ptiles) {
-  const int V = A.V;
-  if (V <= 128) return launch_cn<VARIANT, 1>(st, A, ptiles);
-  if (V <= 256) return launch_cn<VARIANT, 2>(st, A, ptiles);
-  if (V <= 512) return launch_cn<VARIANT, 4>(st, A, ptiles);
-  return launch_cn<VARIANT, 8>(st, A, ptiles);
-}
-template <int VARIANT, bool VEC, typename WT = float, bool SC = false>
-int launch_bonds_elem(hipStream_t st, yk::BondArgs& A, const int32_t* sched = nullptr, int nk = 0);
-template <int VARIANT, bool VEC>
-int launch_bonds_colnorm(RowCfg rc, hipStream_t st, yk::BondArgs& A, int* ptiles) {
-  if (A.V > yk::kRegRows) {  // no workgroup holds a column: streaming forms
-    *ptiles = A.tiles;
-    if constexpr (VARIANT == YUMA_VARIANT_RUST) {
-      A.rowblocks = (A.V + yk::kRustBigRows - 1) / yk::kRustBigRows;
-      A.cblocks = A.tiles;
-      const long long nb = (long long)A.N * A.rowblocks * A.tiles;
-      // one launch pair per epoch: the history countdown (BondArgs::hnext) runs here
-      yk::BondArgs At = A;
-      int hnext = A.hnext, hslot = A.hslot;
-      for (int t = A.t0; t < A.t1; ++t) {
-        const bool hst = A.B_hist != nullptr && t == hnext;
-        At.B_hist = hst ? A.B_hist : nullptr;
-        At.hslot = hslot;
-        YK_LAUNCH((yk::k_rust_big_ema<VEC>), nb, 256, st, At, t, A.cpart);
-        YK_LAUNCH((yk::k_rust_big_norm<VEC>), nb, 256, st, At, t, A.cpart);
-        if (hst) {
-          hnext += A.hstride;
-          ++hslot;
-        }
-      }
-      return yk::DP_TV;
-    } else {
-      return launch_bonds_elem<VARIANT, VEC>(st, A);  // the rank pass formed csb
-    }
-  }
-  if constexpr (VARIANT != YUMA_VARIANT_RUST) {
-    // the rank pass formed the bond column sums: element-wise scan
-    if (A.csb != nullptr && A.Wb_out == nullptr && A.Binst_out == nullptr) {
-      *ptiles = A.tiles;
-      return launch_bonds_elem<VARIANT, VEC>(st, A);
-    }
-  }
-  if constexpr (VEC) {
-    if (A.V > 64 && A.Wb_out == nullptr && A.Binst_out == nullptr) return launch_cn_rows<VARIANT>(st, A, ptiles);
-  }
-  *ptiles = A.tiles;
-  A.rowblocks = 1;
-  A.cblocks = A.tiles;
-  const long long nblocks = (long long)A.N * A.tiles;
-  auto go = [&](auto kern, int nt) { YK_LAUNCH(kern, nblocks, nt, st, A); };
-  with_bool(A.B_hist != nullptr && yk::hist_strided(A), [&](auto HS) {
-    constexpr bool kHs = decltype(HS)::value;
-    switch (rc) {
-      case RC_256_1:
-        go(yk::k_bonds<VARIANT, 256, 1, VEC, kHs>, 256);
-        break;
-      case RC_256_4:
-        go(yk::k_bonds<VARIANT, 256, 4, VEC, kHs>, 256);
-        break;
-      case RC_256_16:
-        go(yk::k_bonds<VARIANT, 256, 16, VEC, kHs>, 256);
-        break;
-      case RC_1024_16:
-        go(yk::k_bonds<VARIANT, 1024, 16, VEC, kHs>, 1024);
-        break;
-    }
-  });
-  return yk::DP_TV;
-}
+constexpr int kCnWaves = 8;
+constexpr int cn_epochs(int R) { return R <= 2 ? 4 : (R == 4 ? 2 : 1); }  // epochs in flight by rows per lane
 
 // Element-wise variants (Yuma3 / Yuma4): R rows x 4 miners per thread, the
 // inputs of the next P epochs in flight, float4 incentive / bond_alpha loads.
@@ -5837,124 +5768,140 @@ constexpr int kWidePCn = 2;    // ... for Yuma / Yuma2 (more work per epoch)
 // with the screened reciprocal 2: 1.25-1.27 against 1.32-1.36 at 3)
 constexpr int kNoHistP2 = 2;
 constexpr int kScanGroup = 4;  // scenarios per block of the shared-input scan
+constexpr int kGrpRows = 2;    // ... and its rows per lane
 // the scans that divide W by k_rowsum's screened reciprocal (rq4) instead of
 // a per-row IEEE reciprocal and a per-element guard: the Yuma / Yuma2 wide
 // history scan (Yuma 1 bonds 1.84 -> 1.73 ms, same box) and the history-less
 // forms (c4 1.32-1.33 -> 1.25-1.27 with 2 epochs in flight, c2 --no-history
 // 0.985-0.997 -> 0.916-0.923; profiles/r05/ab_elem_rq.txt)
 constexpr bool kElemRq(int variant, bool hist) { return hist ? variant <= YUMA_VARIANT_YUMA2 : true; }
-int bonds_rows(bool vec, bool hist, bool wsh) { return vec && (hist || wsh) ? 2 : 1; }
-// sched (with SC): the input schedule and its K stored slices (BondArgsSc)
-template <typename WT, int VARIANT, int R, bool VEC, int P, bool VECI, bool NT, int BS, int CB, int DPL,
-          bool RQ = false, bool HS = false, typename HT = float, bool SC = false>
-int launch_elem_shape(hipStream_t st, yk::BondArgs& A, const int32_t* sched = nullptr, int K = 0) {
-  constexpr int G = BS / (CB / 4);
-  A.rowblocks = (A.V + G * R - 1) / (G * R);
-  A.cblocks = (A.M + CB - 1) / CB;
-  const long long nblocks = (long long)A.N * A.rowblocks * A.cblocks;
-  if constexpr (SC) {
-    yk::BondArgsSc As{};
-    static_cast<yk::BondArgs&>(As) = A;
-    As.sched = sched;
-    As.K = K;
-    YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS, HT, true>), nblocks, BS, st,
-              As);
-  } else
-    YK_LAUNCH((yk::k_bonds_elem<VARIANT, R, VEC, P, VECI, NT, BS, CB, DPL, RQ, WT, HS, HT>), nblocks, BS, st, A);
-  return DPL;
-}
-// WT: the element type A.W addresses (uint16 weights: Yuma 3 / Yuma 4, never
-// the shared-input sweep scan)
+// k_bonds_elem's block shapes in use, yk::ElemShape<R, P, VECI, NT, BS, CB, DPL>
+// (YUMA_ELEM_* name them in a plan). VEC: the shape's incentive / bond_alpha
+// loads follow the scan's vector form.
+// wide history: 2 rows, 512 threads x 1024 miners, non-temporal history stores
+template <int VARIANT>
+using ElemWide =
+    yk::ElemShape<2, (VARIANT <= YUMA_VARIANT_YUMA2 ? kWidePCn : kWideP), true, true, 512, 1024, yk::DP_VQ>;
+// 64-miner tiles, 2 rows: with the history (non-temporal stores) and without
+template <bool VEC>
+using ElemTileHist = yk::ElemShape<2, 2, VEC, true, 256, 64, yk::DP_TV>;
+template <bool VEC>
+using ElemTile = yk::ElemShape<2, 2, VEC, false, 256, 64, yk::DP_TV>;
+// flat 256 threads x 256 miners, epoch-minor quad partials: one row, two rows
+template <bool VEC>
+using ElemFlat1 = yk::ElemShape<1, 4, VEC, false, 256, 256, yk::DP_QTE>;
+template <bool VEC>
+using ElemFlat2 = yk::ElemShape<2, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE>;
+
+// What the choice of a scan depends on.
+struct ScanKey {
+  int variant;
+  bool vec, u16, sched;  // vector form; uint16 W; an input schedule
+  int N, V, M;
+  RowCfg rc;
+  int hist;      // YUMA_SCAN_HIST_NONE / _FP32 / _BF16
+  bool strided;  // yk::hist_strided of the chunk's countdown
+  bool wsh;      // shared inputs
+  bool rq;       // k_rowsum's screened reciprocals at hand (rq4: a run has them, a shard stage does not)
+  bool csb;      // the rank pass formed the bond column sums (forms_csb)
+  bool full;     // W_b or the instantaneous bonds requested
+};
+using ScanPlan = yuma_scan_plan_t;
+
+// The scan of a chunk: its kernel, that kernel's flags, the grid, and the
+// layout and granularity (ptiles: partials per slice and validator) of the
+// dividend partials it writes (k_finalize / k_dsum read them).
+// WT (u16): uint16 weights are Yuma 3 / Yuma 4, never the shared-input sweep scan.
 // A strided history (hist_strided) runs the dense history's shape at every
 // stride, in that shape's HS instantiation ("Strided bond history").
-// A bfloat16 history (BondArgs::hbf16; run_plan admits it for Yuma 3 / Yuma 4
-// in vector form without shared inputs, where a history is written from the
-// wide or the 64-miner-tile shape only) runs the same two shapes with
-// HT = __bf16 ("bfloat16 bond history").
-// SC: the scan under an input schedule of nk stored slices (yuma_sched_native:
-// Yuma 3 / Yuma 4, vector form, no shared inputs, k_rowsum's reciprocals at
-// hand), in the SC instantiation of the shape chosen here. That fixes three
-// choices: no sweep scan, the screened reciprocal, a non-temporal tile history.
-template <int VARIANT, bool VEC, typename WT, bool SC>
-int launch_bonds_elem(hipStream_t st, yk::BondArgs& A, const int32_t* sched, int nk) {
-  const bool hist = A.B_hist != nullptr;
-  const bool hs = hist && yk::hist_strided(A);
-  if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3) {
-    if (A.hbf16) {
-      return with_bool(hs, [&](auto HS) {
-        constexpr bool kHs = decltype(HS)::value;
-        if (A.M >= 1024)
-          return launch_elem_shape<WT, VARIANT, 2, true, kWideP, true, true, 512, 1024, yk::DP_VQ, false, kHs,
-                                   __bf16, SC>(st, A, sched, nk);
-        return launch_elem_shape<WT, VARIANT, 2, true, 2, true, true, 256, 64, yk::DP_TV, false, kHs, __bf16, SC>(
-            st, A, sched, nk);
-      });
+// A bfloat16 history (run_plan admits it for Yuma 3 / Yuma 4 in vector form
+// without shared inputs, where a history is written from the wide or the
+// 64-miner-tile shape only) runs the same two shapes with HT = __bf16
+// ("bfloat16 bond history").
+// SC: the scan under an input schedule (yuma_sched_native: Yuma 3 / Yuma 4,
+// vector form, no shared inputs, k_rowsum's reciprocals at hand), in the SC
+// instantiation of the shape chosen here. That fixes three choices: no sweep
+// scan, the screened reciprocal, a non-temporal tile history.
+ScanPlan plan_scan(const ScanKey& k) {
+  ScanPlan p{};
+  const int tiles = (k.M + yk::kTileM - 1) / yk::kTileM;
+  const bool hist = k.hist != YUMA_SCAN_HIST_NONE;
+  const bool rust = k.variant == YUMA_VARIANT_RUST, colnorm = k.variant <= YUMA_VARIANT_YUMA2;
+  const bool big = k.V > yk::kRegRows;  // no workgroup holds a column: streaming forms
+  p.variant = k.variant;
+  p.vector_form = k.vec;
+  p.w_u16 = k.u16;
+  p.sc = k.sched;
+  p.hist = hist;
+  p.hs = hist && k.strided;
+  p.rc = k.rc;
+  p.ptiles = tiles;
+  p.dpl = yk::DP_TV;
+  // a kernel of `block` threads whose blocks own brows rows x bcols miners of `per` scenarios
+  auto plan = [&](int form, int rows, int block, int brows, int bcols, bool rq, int per = 1) {
+    p.form = form;
+    p.rows = rows;
+    p.block = block;
+    p.rq = rq;
+    p.rowblocks = (k.V + brows - 1) / brows;
+    p.cblocks = (k.M + bcols - 1) / bcols;
+    p.grid = (long long)((k.N + per - 1) / per) * p.rowblocks * p.cblocks;
+    return p;
+  };
+  // one launch pair per epoch
+  if (rust && big) return plan(YUMA_SCAN_RUST_BIG, 0, 256, yk::kRustBigRows, yk::kTileM, false);
+  // Yuma / Yuma2 whose rank pass formed the bond column sums (always above
+  // kRegRows validators) take the element-wise scan
+  if (colnorm && !(!rust && (big || (k.csb && !k.full)))) {
+    if (k.vec && k.V > 64 && !k.full) {
+      // RQ: k_rowsum's screened reciprocals (run_impl; not the shard stages)
+      plan(YUMA_SCAN_STRIP, k.V <= 128 ? 1 : k.V <= 256 ? 2 : k.V <= 512 ? 4 : 8, 64 * kCnWaves, k.V, yk::kCnStrip, k.rq);
+      p.ptiles = p.cblocks;
+      return p;
     }
+    return plan(YUMA_SCAN_TILE, k.rc == RC_256_1 ? 1 : k.rc == RC_256_4 ? 4 : 16, k.rc == RC_1024_16 ? 1024 : 256, k.V,
+                yk::kTileM, false);
   }
-  if constexpr (VEC) {
-    if (hist && A.M >= 1024) {
-      constexpr int P = VARIANT <= YUMA_VARIANT_YUMA2 ? kWidePCn : kWideP;
-      return with_bool(kElemRq(VARIANT, true) && A.rq4 != nullptr, [&](auto RQ) {
-        constexpr bool kRq = kElemRq(VARIANT, true) && decltype(RQ)::value;
-        return with_bool(hs, [&](auto HS) {
-          return launch_elem_shape<WT, VARIANT, 2, true, P, true, true, 512, 1024, yk::DP_VQ, kRq,
-                                   decltype(HS)::value, float, SC>(st, A, sched, nk);
-        });
-      });
-    }
+  // k_bonds_elem in the shape sh (what sizes the grid is the same for every variant and vector form)
+  auto elem = [&](int shape, auto sh, bool rq) {
+    using SH = decltype(sh);
+    p.shape = shape;
+    p.nt = SH::NT;
+    p.dpl = SH::DPL;
+    return plan(YUMA_SCAN_ELEM, SH::R, SH::BS, SH::BS / (SH::CB / 4) * SH::R, SH::CB, rq);
+  };
+  const bool wide = k.M >= 1024;  // a history in vector form: the wide shape from here, else the 64-miner tiles
+  auto wide_or_tile = [&](bool rq) {
+    return wide ? elem(YUMA_ELEM_WIDE, ElemWide<YUMA_VARIANT_YUMA3>{}, rq)
+                : elem(YUMA_ELEM_TILE_HIST, ElemTileHist<true>{}, false);
+  };
+  if (k.vec && !colnorm && k.hist == YUMA_SCAN_HIST_BF16) {
+    p.hist_bf16 = 1;
+    return wide_or_tile(false);
   }
-  if constexpr (VEC && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float> && !SC) {
-    if (A.wsh && A.N >= 2 && A.rq4 != nullptr) {  // a sweep over one input trajectory
-      constexpr int K = kScanGroup, R = 2;
-      A.rowblocks = (A.V + 16 * R - 1) / (16 * R);
-      A.cblocks = A.tiles;
-      const long long nblocks = (long long)((A.N + K - 1) / K) * A.rowblocks * A.tiles;
-      if (hs)
-        YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, true, true>), nblocks, 256, st, A);
-      else
-        with_bool(hist, [&](auto HIST) {
-          YK_LAUNCH((yk::k_bonds_grp<VARIANT, K, R, 2, decltype(HIST)::value>), nblocks, 256, st, A);
-        });
-      return yk::DP_TV;
-    }
-  }
-  if (bonds_rows(VEC, hist, A.wsh != 0) != 2) {
+  if (k.vec && hist && wide) return wide_or_tile(kElemRq(k.variant, true) && k.rq);
+  if (k.vec && !colnorm && !k.u16 && !k.sched && k.wsh && k.N >= 2 && k.rq)  // a sweep over one input trajectory
+    return plan(YUMA_SCAN_GRP, kGrpRows, 256, 16 * kGrpRows, yk::kTileM, true, kScanGroup);
+  if (!(k.vec && (hist || k.wsh))) {
     // two rows per lane (one incentive load per two rows, 2 epochs in
     // flight) once the grid has blocks to spare: c4 1.41 -> 1.38 ms; with
     // c2's 512 such blocks 0.99 -> 1.31, so one row per lane there
-    const long long blocks_r2 = (long long)A.N * ((A.V + 7) / 8) * ((A.M + 255) / 256);
-    constexpr bool kRqOk = VEC && kElemRq(VARIANT, false);
-    if constexpr (!VEC) {  // the scalar form writes its history from these shapes
-      if (hs) {
-        if (blocks_r2 >= 4096)
-          return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, false, true>(st, A);
-        return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, false, true>(st, A);
-      }
-    }
-    auto go = [&](auto RQ) {
-      constexpr bool kRq = kRqOk && decltype(RQ)::value;
-      if (blocks_r2 >= 4096)
-        return launch_elem_shape<WT, VARIANT, 2, VEC, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE, kRq, false, float,
-                                 SC>(st, A, sched, nk);
-      return launch_elem_shape<WT, VARIANT, 1, VEC, 4, VEC, false, 256, 256, yk::DP_QTE, kRq, false, float, SC>(
-          st, A, sched, nk);
-    };
-    if constexpr (SC)
-      return go(std::true_type{});
-    else
-      return with_bool(kRqOk && A.rq4 != nullptr, go);
+    const long long blocks_r2 = (long long)k.N * ((k.V + 7) / 8) * ((k.M + 255) / 256);
+    // (the scalar form writes its history from these shapes; under a
+    // schedule the reciprocals are at hand)
+    const bool rq = k.vec && kElemRq(k.variant, false) && (k.sched || k.rq);
+    return blocks_r2 >= 4096 ? elem(YUMA_ELEM_FLAT2, ElemFlat2<true>{}, rq) : elem(YUMA_ELEM_FLAT1, ElemFlat1<true>{}, rq);
   }
   // the 64-miner tiles; the history goes out with non-temporal stores
-  auto tile = [&](auto NT, auto HS) {
-    return launch_elem_shape<WT, VARIANT, 2, VEC, 2, VEC, decltype(NT)::value, 256, 64, yk::DP_TV, false,
-                             decltype(HS)::value, float, SC>(st, A, sched, nk);
-  };
-  if (hs) return tile(std::true_type{}, std::true_type{});
-  if constexpr (SC)  // (without a history a schedule run took the forms above)
-    return tile(std::true_type{}, std::false_type{});
-  else
-    return with_bool(hist, [&](auto HIST) { return tile(HIST, std::false_type{}); });
+  // (without a history a schedule run took the forms above)
+  return hist || k.sched ? elem(YUMA_ELEM_TILE_HIST, ElemTileHist<true>{}, false)
+                         : elem(YUMA_ELEM_TILE, ElemTile<true>{}, false);
 }
+
+// (Defined behind shard_stage_impl, the first caller in the file: the scans are
+// instantiated where launch_scan is defined, and so keep their place in the
+// code object, behind the kernels of phase 1.)
+void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K);
 
 // The watched columns' scan over the chunk of A (k_bonds_watch), from the main
 // scan's own arguments: the same inputs, state and history countdown. Enqueued
@@ -5993,25 +5940,6 @@ void launch_watch(hipStream_t st, int variant, const yk::BondArgs& A, const int3
     else
       YK_LAUNCH((yk::k_bonds_watch<YUMA_VARIANT_YUMA4, WT, kSc>), nblocks, yk::kWatchBS, st, X);
   });
-}
-
-// Launch the bond scan for A.N scenarios over epochs [A.t0, A.t1); returns
-// the layout of the dividend partials it wrote (k_finalize / k_dsum read it).
-template <bool VEC>
-int launch_bonds(int variant, RowCfg rc, hipStream_t st, yk::BondArgs& A, int* ptiles) {
-  *ptiles = A.tiles;
-  switch (variant) {
-    case YUMA_VARIANT_RUST:
-      return launch_bonds_colnorm<YUMA_VARIANT_RUST, VEC>(rc, st, A, ptiles);
-    case YUMA_VARIANT_YUMA1:
-      return launch_bonds_colnorm<YUMA_VARIANT_YUMA1, VEC>(rc, st, A, ptiles);
-    case YUMA_VARIANT_YUMA2:
-      return launch_bonds_colnorm<YUMA_VARIANT_YUMA2, VEC>(rc, st, A, ptiles);
-    case YUMA_VARIANT_YUMA3:
-      return launch_bonds_elem<YUMA_VARIANT_YUMA3, VEC>(st, A);
-    default:
-      return launch_bonds_elem<YUMA_VARIANT_YUMA4, VEC>(st, A);
-  }
 }
 
 // Optional per-phase timing (bench / roofline): a HIP event is recorded on the
@@ -6127,11 +6055,12 @@ Bufs pick_bufs(const yuma_outputs_t* out, const Workspace& ws) {
 // column sums Σ_v S·W_b, so that the bond scan is element-wise? Above kRegRows
 // validators always (the element-wise scan is the only one there, and it
 // writes W_b / B_inst itself); else for run outputs above 64 validators, with
-// no matrix of the full outputs asked for (ws.tvc: T_v).
-bool forms_csb(const Workspace& ws, int V, const yuma_outputs_t* out) {
-  if (ws.csb == nullptr) return false;
+// no matrix of the full outputs asked for. (By the variant and out->Tv, as
+// carve() gives the workspace csb and tvc: yuma_scan_plan asks without one.)
+bool forms_csb(int variant, int V, const yuma_outputs_t* out) {
+  if (variant != YUMA_VARIANT_YUMA1 && variant != YUMA_VARIANT_YUMA2) return false;
   if (V > yk::kRegRows) return true;
-  return V > 64 && out->Wn == nullptr && out->Wc == nullptr && ws.tvc == nullptr && out->Wb == nullptr &&
+  return V > 64 && out->Wn == nullptr && out->Wc == nullptr && out->Tv == nullptr && out->Wb == nullptr &&
          out->B_inst == nullptr;
 }
 
@@ -6215,6 +6144,41 @@ struct RunReq {
   float* B_watch = nullptr;
 };
 
+// The history countdown (BondArgs::hnext) of the chunk from epoch A.t0 of the
+// run q: epochs count from the run's epoch 0, so the slot follows the absolute epoch
+void hist_countdown(const RunReq& q, yk::BondArgs* A) {
+  const int c0 = A->t0, E = q.E;
+  const long long j = c0 <= q.hist_first ? 0 : ((long long)c0 - q.hist_first + q.hist_stride - 1) / q.hist_stride;
+  const long long next = q.hist_first + j * q.hist_stride;
+  A->hstride = q.hist_stride < E ? q.hist_stride : E;
+  A->hnext = next < E ? (int)next : -1;
+  A->hslot = next < E ? (int)j : 0;
+}
+
+// plan_scan's key for a chunk of the run q (of q it reads the sizes, the
+// resolved options and out's pointers for NULL). vec: the vector form; sched:
+// under an input schedule; run: a run, whose k_rowsum leaves the screened
+// reciprocals (rq4), where a shard stage has none; strided: yk::hist_strided
+// of the chunk's countdown, as the launch's BondArgs holds it.
+ScanKey scan_key(const RunReq& q, bool vec, bool sched, bool run, bool strided) {
+  ScanKey k{};
+  k.variant = q.variant;
+  k.vec = vec;
+  k.u16 = q.w_u16 != 0;
+  k.sched = sched;
+  k.N = q.N;
+  k.V = q.V;
+  k.M = q.M;
+  k.rc = row_cfg(q.V);
+  k.hist = q.out->B_hist == nullptr ? YUMA_SCAN_HIST_NONE : q.hist_bf16 ? YUMA_SCAN_HIST_BF16 : YUMA_SCAN_HIST_FP32;
+  k.strided = strided;
+  k.wsh = q.wsh != 0;
+  k.rq = run;
+  k.csb = forms_csb(q.variant, q.V, q.out);
+  k.full = q.out->Wb != nullptr || q.out->B_inst != nullptr;
+  return k;
+}
+
 // What run_plan resolves for run_impl: the carved workspace (wk: the staging
 // set of an input schedule's K stored slices), the vector form, the shapes.
 struct RunPlan {
@@ -6224,36 +6188,14 @@ struct RunPlan {
   RowCfg rc;
 };
 
-// Validate: every refusal of a run, in the order the entry points document,
-// without a HIP call -- so that a capture is refused before it opens
-// (graph_create_impl) by the code and text the direct run returns.
-int run_plan(const RunReq& q, RunPlan* p) {
-  const int variant = q.variant, N = q.N, E = q.E, V = q.V, M = q.M, K = q.K, wsh = q.wsh;
+// The three native refusals of a run (schedule, bfloat16 history, uint16 W),
+// each followed by its alignment refusal, and the watch list's beside the
+// schedule's: run_plan's last step, and yuma_scan_plan's. sched, K: under an
+// input schedule of K stored slices.
+int check_native(const RunReq& q, bool vec, bool sched, int K) {
+  const int variant = q.variant, N = q.N, E = q.E, V = q.V, M = q.M, wsh = q.wsh;
   const yuma_outputs_t* out = q.out;
-  if (const int err = check_sizes(variant, N, E, V, M)) return err;
-  if ((M + yk::kTileM - 1) / yk::kTileM > yk::kMaxTiles) return fail(YUMA_EINVAL, "M too large");
-  if (!q.prm || !q.W || !q.S || !out || !q.workspace) return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
-  if (q.sched != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
-  if (q.sched == nullptr && K != 0) return fail(YUMA_EINVAL, "K=%d stored slices without a schedule pointer", K);
-  if (q.has_watch) {
-    if (q.n_watch < 1) return fail(YUMA_EINVAL, "n_watch=%d watched columns: at least one is required", q.n_watch);
-    if (q.watch == nullptr || q.B_watch == nullptr) return fail(YUMA_EINVAL, "the watch list or B_watch is NULL");
-    // (k_bonds_watch: one wave per block, N blocks-per-scenario blocks)
-    if (((long long)V * q.n_watch + yk::kWatchBS - 1) / yk::kWatchBS * N > INT_MAX)
-      return fail(YUMA_EINVAL, "n_watch=%d: N V n_watch elements exceed the watch kernel's grid", q.n_watch);
-  }
-  const int full = out->Tv != nullptr;
-  // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
-  // params live in device memory, so the Python marshaller enforces it.
-  p->ws = carve((char*)q.workspace, variant, N, E, V, M, full);
-  p->wk = q.sched ? carve((char*)q.workspace + p->ws.bytes, variant, N, K, V, M, 0, true) : Workspace{};
-  if (p->ws.bytes + p->wk.bytes > q.ws_bytes)
-    return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)",
-                q.ws_bytes, p->ws.bytes + p->wk.bytes, full);
-  p->tiles = (M + yk::kTileM - 1) / yk::kTileM;
-  p->rc = row_cfg(V);
-  const bool vec = p->vec = vector_form(M, q.W, q.B_init, q.Wprev_init, out, q.hist_bf16 != 0, q.w_u16 ? 2 : 4);
-  if (q.sched != nullptr) {  // (the uint16 / bfloat16 tests of their own follow)
+  if (sched) {  // (the uint16 / bfloat16 tests of their own follow)
     const int f = wsh ? YUMA_RUN_SHARED_INPUTS : 0;
     if (!sched_native(variant, N, E, K, V, M, out, f))
       return fail(YUMA_EUNSUPPORTED,
@@ -6295,6 +6237,56 @@ int run_plan(const RunReq& q, RunPlan* p) {
   return YUMA_OK;
 }
 
+// The tile limit of a run's M (run_plan, yuma_scan_plan)
+int check_tiles(int M) {
+  return (M + yk::kTileM - 1) / yk::kTileM > yk::kMaxTiles ? fail(YUMA_EINVAL, "M too large") : YUMA_OK;
+}
+
+// A request of sizes and outputs alone, every option at its default (the
+// dense fp32 history, no shared inputs): what a shard stage is to scan_key
+RunReq size_req(int variant, int N, int E, int V, int M, const yuma_outputs_t* out) {
+  RunReq q{};
+  q.variant = variant;
+  q.N = N;
+  q.E = E;
+  q.V = V;
+  q.M = M;
+  q.out = out;
+  return q;
+}
+
+// Validate: every refusal of a run, in the order the entry points document,
+// without a HIP call -- so that a capture is refused before it opens
+// (graph_create_impl) by the code and text the direct run returns.
+int run_plan(const RunReq& q, RunPlan* p) {
+  const int variant = q.variant, N = q.N, E = q.E, V = q.V, M = q.M, K = q.K;
+  const yuma_outputs_t* out = q.out;
+  if (const int err = check_sizes(variant, N, E, V, M)) return err;
+  if (const int err = check_tiles(M)) return err;
+  if (!q.prm || !q.W || !q.S || !out || !q.workspace) return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
+  if (q.sched != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
+  if (q.sched == nullptr && K != 0) return fail(YUMA_EINVAL, "K=%d stored slices without a schedule pointer", K);
+  if (q.has_watch) {
+    if (q.n_watch < 1) return fail(YUMA_EINVAL, "n_watch=%d watched columns: at least one is required", q.n_watch);
+    if (q.watch == nullptr || q.B_watch == nullptr) return fail(YUMA_EINVAL, "the watch list or B_watch is NULL");
+    // (k_bonds_watch: one wave per block, N blocks-per-scenario blocks)
+    if (((long long)V * q.n_watch + yk::kWatchBS - 1) / yk::kWatchBS * N > INT_MAX)
+      return fail(YUMA_EINVAL, "n_watch=%d: N V n_watch elements exceed the watch kernel's grid", q.n_watch);
+  }
+  const int full = out->Tv != nullptr;
+  // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
+  // params live in device memory, so the Python marshaller enforces it.
+  p->ws = carve((char*)q.workspace, variant, N, E, V, M, full);
+  p->wk = q.sched ? carve((char*)q.workspace + p->ws.bytes, variant, N, K, V, M, 0, true) : Workspace{};
+  if (p->ws.bytes + p->wk.bytes > q.ws_bytes)
+    return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)",
+                q.ws_bytes, p->ws.bytes + p->wk.bytes, full);
+  p->tiles = (M + yk::kTileM - 1) / yk::kTileM;
+  p->rc = row_cfg(V);
+  const bool vec = p->vec = vector_form(M, q.W, q.B_init, q.Wprev_init, out, q.hist_bf16 != 0, q.w_u16 ? 2 : 4);
+  return check_native(q, vec, q.sched != nullptr, K);
+}
+
 // Enqueue the run that run_plan admitted, on q.stream. WT: the element type
 // of W, float or (YUMA_RUN_W_U16) uint16_t; slices and rows are indexed in elements.
 // Under an input schedule phase 1 runs once per stored slice into the staging
@@ -6306,7 +6298,7 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
   constexpr bool U16 = std::is_same_v<WT, uint16_t>;
   static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
   const int variant = q.variant, N = q.N, E = q.E, V = q.V, M = q.M, K = q.K, wsh = q.wsh;
-  const int hist_stride = q.hist_stride, hist_first = q.hist_first, tiles = plan.tiles, chunk0 = q.chunk;
+  const int tiles = plan.tiles, chunk0 = q.chunk;
   const RowCfg rc = plan.rc;
   const yuma_params_t* prm = q.prm;
   const WT* W = static_cast<const WT*>(q.W);
@@ -6346,7 +6338,7 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
   const bool mc = crep != nullptr && V <= 256;
   if (mc) YK_LAUNCH(yk::k_class_list, 1, 256, st, ws.crep, N, ws.clist);
   const bool streaming = out->Wn == nullptr && out->Wc == nullptr && ws.tvc == nullptr;
-  float* csb = forms_csb(ws, V, out) ? ws.csb : nullptr;
+  float* csb = forms_csb(variant, V, out) ? ws.csb : nullptr;
   const bool rank_stream = streaming && variant != YUMA_VARIANT_YUMA2;  // Yuma2's W_prev: rank per scenario
   const int* rcrep = rank_stream ? crep : nullptr;
   if (rcrep != nullptr && csb != nullptr) {  // the column sums depend on bond_penalty too
@@ -6465,28 +6457,14 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     A.t1 = c1;
     A.wsh = wsh;
     A.hbf16 = q.hist_bf16;
-    {
-      // the history countdown of this chunk (BondArgs::hnext): epochs count
-      // from the run's epoch 0, so the slot follows the absolute epoch
-      const long long j = c0 <= hist_first ? 0 : ((long long)c0 - hist_first + hist_stride - 1) / hist_stride;
-      const long long next = hist_first + j * hist_stride;
-      A.hstride = hist_stride < E ? hist_stride : E;
-      A.hnext = next < E ? (int)next : -1;
-      A.hslot = next < E ? (int)j : 0;
-    }
+    hist_countdown(q, &A);
     tm.mark(YUMA_PHASE_BONDS);
     if (q.has_watch)  // (Yuma 3 / Yuma 4: run_plan) the state before epoch c0 is still in A.Bstate
       launch_watch<WT>(st, variant, A, q.watch, q.n_watch, q.B_watch, sched, K);
-    int ptiles = tiles;
-    int dpl;
-    if (sched != nullptr)  // (Yuma 3 / Yuma 4 in vector form: run_plan)
-      dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem<YUMA_VARIANT_YUMA3, true, WT, true>(st, A, sched, K)
-                                          : launch_bonds_elem<YUMA_VARIANT_YUMA4, true, WT, true>(st, A, sched, K);
-    else if constexpr (U16)
-      dpl = variant == YUMA_VARIANT_YUMA3 ? launch_bonds_elem<YUMA_VARIANT_YUMA3, true, WT>(st, A)
-                                          : launch_bonds_elem<YUMA_VARIANT_YUMA4, true, WT>(st, A);
-    else
-      dpl = with_bool(vec, [&](auto VEC) { return launch_bonds<decltype(VEC)::value>(variant, rc, st, A, &ptiles); });
+    const ScanPlan scan = plan_scan(scan_key(q, vec, sched != nullptr, true, yk::hist_strided(A)));
+    launch_scan(st, scan, A, sched, K);
+    const int ptiles = scan.ptiles;
+    int dpl = scan.dpl;
     tm.mark(YUMA_PHASE_FINALIZE);
     const float* dsrc = ws.dpart;
     if (dpl == yk::DP_QTE) {
@@ -6555,7 +6533,7 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
   const long long ns = (long long)E * N;
   // Yuma / Yuma2: the bond column sums are sums over validators, local to
   // the shard's columns: formed by stage 3's rank pass, read by stage 4's scan
-  float* shard_csb = forms_csb(ws, V, out) ? ws.csb : nullptr;
+  float* shard_csb = forms_csb(variant, V, out) ? ws.csb : nullptr;
   switch (stage) {
     case 1: {
       if (!io->rowsum_part) return fail(YUMA_EINVAL, "stage 1 needs io->rowsum_part");
@@ -6609,9 +6587,10 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
       YK_LAUNCH(yk::k_incentive, ns * ich, 256, st, R, ws.rpart, out->P, M, 0LL, tiles, I,
                 out->P ? out->T : nullptr, ws.scal, io->rsum, nullptr, N, ich, incentive_v4(M, R, I, out), 1);
       yk::BondArgs A = bond_args(W, ws, buf, prm, B_init, Wprev_init, out, shard_csb, N, E, V, M);
-      int ptiles = tiles;
-      const int dpl =
-          with_bool(vec, [&](auto VEC) { return launch_bonds<decltype(VEC)::value>(variant, rc, st, A, &ptiles); });
+      // (no options, no screened reciprocals)
+      const ScanPlan scan = plan_scan(scan_key(size_req(variant, N, E, V, M, out), vec, false, false, yk::hist_strided(A)));
+      launch_scan(st, scan, A, nullptr, 0);
+      const int ptiles = scan.ptiles, dpl = scan.dpl;
       if (dpl == yk::DP_QTE)
         YK_LAUNCH(yk::k_dte_sum, (long long)N * ((E + 15) / 16) * ((V + 3) / 4), 256, st, ws.dpart, N, V,
                   ptiles, A.ep, 0, E, io->dsum_part);
@@ -6635,6 +6614,183 @@ int shard_stage_impl(int stage, int variant, const yuma_params_t* prm, int N, in
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(YUMA_EHIP, "HIP launch failed: %s", hipGetErrorString(e));
   return YUMA_OK;
+}
+
+[[noreturn]] void bad_plan(const ScanPlan& p) {
+  fprintf(stderr, "yuma: no bond scan is instantiated for variant=%d vec=%d u16=%d sc=%d form=%d shape=%d rows=%d rc=%d "
+          "rq=%d hs=%d hist=%d bf16=%d\n", p.variant, p.vector_form, p.w_u16, p.sc, p.form, p.shape, p.rows, p.rc, p.rq,
+          p.hs, p.hist, p.hist_bf16);
+  abort();
+}
+
+// The variant as a template argument: f(std::integral_constant<int, variant>{})
+template <typename F>
+void with_variant(int variant, F&& f) {
+  if (variant == YUMA_VARIANT_RUST) return f(std::integral_constant<int, YUMA_VARIANT_RUST>{});
+  if (variant == YUMA_VARIANT_YUMA1) return f(std::integral_constant<int, YUMA_VARIANT_YUMA1>{});
+  if (variant == YUMA_VARIANT_YUMA2) return f(std::integral_constant<int, YUMA_VARIANT_YUMA2>{});
+  if (variant == YUMA_VARIANT_YUMA3) return f(std::integral_constant<int, YUMA_VARIANT_YUMA3>{});
+  return f(std::integral_constant<int, YUMA_VARIANT_YUMA4>{});
+}
+
+// A plan's flag as a template argument, where the kernel at hand is
+// instantiated for it: MODE kEither both values, kNever false only, kAlways
+// true only. A flag outside its mode is a plan outside the instantiated set.
+enum FlagMode { kNever, kEither, kAlways };
+template <int MODE, typename F>
+void with_flag(const ScanPlan& p, int flag, F&& f) {
+  if constexpr (MODE == kEither) {
+    with_bool(flag != 0, f);
+  } else {
+    if ((flag != 0) != (MODE == kAlways)) bad_plan(p);
+    f(std::integral_constant<bool, MODE == kAlways>{});
+  }
+}
+template <int MODE>
+using Mode = std::integral_constant<int, MODE>;
+
+// launch_scan for one variant, vector form, W element type and schedule flag:
+// from the plan's form, shape and flags to the instantiation. The modes
+// written at each kernel are the instantiated set, in this one place; any
+// other plan aborts (bad_plan).
+template <int VARIANT, bool VEC, typename WT, bool SC>
+void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K) {
+  constexpr bool kPlain = std::is_same_v<WT, float> && !SC;  // fp32 W, no schedule
+  constexpr bool kColnorm = VARIANT <= YUMA_VARIANT_YUMA2, kElem34 = VARIANT >= YUMA_VARIANT_YUMA3;
+  const long long nb = p.grid;
+  [[maybe_unused]] auto go = [&](auto kern) { YK_LAUNCH(kern, nb, p.block, st, A); };
+  if constexpr (kColnorm && kPlain) {
+    if (p.form == YUMA_SCAN_TILE && !p.rq)  // k_bonds, by RowCfg
+      return with_bool(p.hs != 0, [&](auto HS) {
+        constexpr bool kHs = decltype(HS)::value;
+        switch (p.rc) {
+          case RC_256_1:
+            return go(yk::k_bonds<VARIANT, 256, 1, VEC, kHs>);
+          case RC_256_4:
+            return go(yk::k_bonds<VARIANT, 256, 4, VEC, kHs>);
+          case RC_256_16:
+            return go(yk::k_bonds<VARIANT, 256, 16, VEC, kHs>);
+          case RC_1024_16:
+            return go(yk::k_bonds<VARIANT, 1024, 16, VEC, kHs>);
+        }
+        bad_plan(p);
+      });
+    if constexpr (VEC) {
+      if (p.form == YUMA_SCAN_STRIP && p.block == 64 * kCnWaves)  // k_bonds_cn, by rows per lane
+        return with_bool(p.rq != 0, [&](auto RQ) {
+          with_bool(p.hs != 0, [&](auto HS) {
+            constexpr bool kRq = decltype(RQ)::value, kHs = decltype(HS)::value;
+            switch (p.rows) {
+              case 1:
+                return go(yk::k_bonds_cn<VARIANT, 1, cn_epochs(1), kCnWaves, kRq, kHs>);
+              case 2:
+                return go(yk::k_bonds_cn<VARIANT, 2, cn_epochs(2), kCnWaves, kRq, kHs>);
+              case 4:
+                return go(yk::k_bonds_cn<VARIANT, 4, cn_epochs(4), kCnWaves, kRq, kHs>);
+              case 8:
+                return go(yk::k_bonds_cn<VARIANT, 8, cn_epochs(8), kCnWaves, kRq, kHs>);
+            }
+            bad_plan(p);
+          });
+        });
+    }
+  }
+  if constexpr (VARIANT == YUMA_VARIANT_RUST && kPlain) {
+    if (p.form == YUMA_SCAN_RUST_BIG) {
+      // one launch pair per epoch: the history countdown (BondArgs::hnext) runs here
+      yk::BondArgs At = A;
+      int hnext = A.hnext, hslot = A.hslot;
+      for (int t = A.t0; t < A.t1; ++t) {
+        const bool hst = A.B_hist != nullptr && t == hnext;
+        At.B_hist = hst ? A.B_hist : nullptr;
+        At.hslot = hslot;
+        YK_LAUNCH((yk::k_rust_big_ema<VEC>), nb, 256, st, At, t, A.cpart);
+        YK_LAUNCH((yk::k_rust_big_norm<VEC>), nb, 256, st, At, t, A.cpart);
+        if (hst) {
+          hnext += A.hstride;
+          ++hslot;
+        }
+      }
+      return;
+    }
+  }
+  if constexpr (kElem34 && VEC && kPlain) {
+    if (p.form == YUMA_SCAN_GRP && p.rq && (p.hist || !p.hs)) {  // the sweep scan; HS only with HIST
+      if (p.hs) return go(yk::k_bonds_grp<VARIANT, kScanGroup, kGrpRows, 2, true, true>);
+      return with_bool(p.hist != 0, [&](auto HIST) {
+        go(yk::k_bonds_grp<VARIANT, kScanGroup, kGrpRows, 2, decltype(HIST)::value>);
+      });
+    }
+  }
+  if constexpr (VARIANT != YUMA_VARIANT_RUST) {
+    // k_bonds_elem in the shape sh, with the plan's RQ, HS and bfloat16 history where
+    // the modes admit them. sched (with SC): the input schedule and its K
+    // stored slices (BondArgsSc)
+    auto elem = [&](auto sh, auto rq_mode, auto hs_mode, auto bf16_mode) {
+      using SH = decltype(sh);
+      with_flag<decltype(rq_mode)::value>(p, p.rq, [&](auto RQ) {
+        with_flag<decltype(hs_mode)::value>(p, p.hs, [&](auto HS) {
+          with_flag<decltype(bf16_mode)::value>(p, p.hist_bf16, [&](auto BF16) {
+            using HT = std::conditional_t<decltype(BF16)::value, __bf16, float>;
+            constexpr bool kRq = decltype(RQ)::value, kHs = decltype(HS)::value;
+            if constexpr (SC) {
+              yk::BondArgsSc As{};
+              static_cast<yk::BondArgs&>(As) = A;
+              As.sched = sched;
+              As.K = K;
+              YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, VEC, kRq, WT, kHs, HT, true>), nb, SH::BS, st, As);
+            } else
+              YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, VEC, kRq, WT, kHs, HT>), nb, SH::BS, st, A);
+          });
+        });
+      });
+    };
+    // the flat shapes. Scalar form: no RQ, and a strided history is written
+    // from them; vector form: no history, RQ as planned, under a schedule always
+    constexpr Mode<(!VEC ? kNever : SC ? kAlways : kEither)> flat_rq{};
+    constexpr Mode<(kElem34 && VEC ? kEither : kNever)> bf16{};  // bfloat16: Yuma 3 / Yuma 4 in vector form
+    constexpr Mode<kNever> never{};
+    constexpr Mode<kEither> either{};
+    if (p.form == YUMA_SCAN_ELEM) switch (p.shape) {
+        case YUMA_ELEM_WIDE:  // vector form; RQ for Yuma / Yuma2 (kElemRq)
+          if constexpr (VEC)
+            return elem(ElemWide<VARIANT>{}, Mode<(kElemRq(VARIANT, true) ? kEither : kNever)>{}, either, bf16);
+          break;
+        case YUMA_ELEM_TILE_HIST:
+          return elem(ElemTileHist<VEC>{}, never, either, bf16);
+        case YUMA_ELEM_TILE:  // no schedule
+          if constexpr (!SC) return elem(ElemTile<VEC>{}, never, never, never);
+          break;
+        case YUMA_ELEM_FLAT1:
+          return elem(ElemFlat1<VEC>{}, flat_rq, Mode<(VEC ? kNever : kEither)>{}, never);
+        case YUMA_ELEM_FLAT2:
+          return elem(ElemFlat2<VEC>{}, flat_rq, Mode<(VEC ? kNever : kEither)>{}, never);
+      }
+  }
+  bad_plan(p);
+}
+
+// Launch the bond scan that plan_scan chose, for A.N scenarios over epochs
+// [A.t0, A.t1): the only place a bond scan is instantiated. uint16 weights
+// and input schedules are Yuma 3 / Yuma 4 in vector form (run_plan).
+void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K) {
+  A.rowblocks = p.rowblocks;
+  A.cblocks = p.cblocks;
+  if ((p.rq && A.rq4 == nullptr) || (p.sc && sched == nullptr)) bad_plan(p);
+  with_variant(p.variant, [&](auto VARIANT) {
+    constexpr int kVariant = decltype(VARIANT)::value;
+    if constexpr (kVariant >= YUMA_VARIANT_YUMA3) {
+      if (p.vector_form && p.w_u16)
+        return with_bool(p.sc != 0, [&](auto SC) {
+          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K);
+        });
+      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K);
+    }
+    if (p.w_u16 || p.sc) bad_plan(p);
+    with_bool(p.vector_form != 0, [&](auto VEC) {
+      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K);
+    });
+  });
 }
 
 }  // namespace
@@ -6815,6 +6971,30 @@ int yuma_u16_native(int variant, int N, int E, int V, int M, const yuma_outputs_
 
 int yuma_hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
   return hist_bf16_native(variant, N, E, V, M, out, flags) ? 1 : 0;
+}
+
+static_assert(YUMA_DP_TV == yk::DP_TV && YUMA_DP_VQ == yk::DP_VQ && YUMA_DP_QTE == yk::DP_QTE,
+              "yuma_scan_plan_t.dpl reports DpLayout");
+static_assert(sizeof(yuma_scan_plan_t) == 80, "yuma_scan_plan_t: one 64-bit word and 18 ints");
+
+int yuma_scan_plan(int variant, int N, int E, int V, int M, const yuma_outputs_t* out,
+                   const yuma_run_options_t* opts, int vector_form, int has_sched, int shard_stage,
+                   yuma_scan_plan_t* plan) {
+  if (plan == nullptr || out == nullptr) return fail(YUMA_EINVAL, "yuma_scan_plan: out or plan is NULL");
+  if (const int err = check_sizes(variant, N, E, V, M)) return err;
+  RunReq q = size_req(variant, N, E, V, M, out);
+  const bool vec = vector_form != 0, sched = has_sched != 0, run = shard_stage == 0;
+  if (run) {  // what a run refuses, by run_plan's own steps (K: sched_native asks for one stored slice at least)
+    if (const int err = read_opts(opts, &q)) return err;
+    if (const int err = check_tiles(M)) return err;
+    if (const int err = check_native(q, vec, sched, sched ? 1 : 0)) return err;
+  } else if (opts != nullptr || sched) {
+    return fail(YUMA_EINVAL, "yuma_scan_plan: a shard stage takes no options and no schedule");
+  }
+  yk::BondArgs first{};  // the countdown of the chunk from epoch 0
+  hist_countdown(q, &first);
+  *plan = plan_scan(scan_key(q, vec, sched, run, yk::hist_strided(first)));
+  return YUMA_OK;
 }
 
 int yuma_run_profiled(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,

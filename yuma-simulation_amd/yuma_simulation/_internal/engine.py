@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "yuma_run_watch",
     "yuma_watch_native",
     "yuma_graph_create_watch",
+    "yuma_scan_plan",
     "yuma_epoch",
     "yuma_synth_weights",
     "yuma_shard_stage",
@@ -230,6 +231,9 @@ def load_library(path: str | None = None):
             lib.yuma_graph_create_watch.restype = i32
             lib.yuma_watch_native.argtypes = [i32, i32, i32, i32, i32, i32, i32]
             lib.yuma_watch_native.restype = i32
+        if hasattr(lib, "yuma_scan_plan"):  # (A/B libraries of older sources lack it)
+            lib.yuma_scan_plan.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp]
+            lib.yuma_scan_plan.restype = i32
         lib.yuma_graph_launch.argtypes = [vp, vp]
         lib.yuma_graph_launch.restype = i32
         lib.yuma_graph_nodes.argtypes = [vp]
@@ -559,6 +563,73 @@ def watch_native(variant: int, N: int, E: int, V: int, M: int, n_watch: int, *, 
     `run` writes an fp32 history and gathers the columns, and RunGraph refuses."""
     flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
     return bool(load_library().yuma_watch_native(variant, N, E, V, M, n_watch, flags))
+
+
+class YumaScanPlanC(ctypes.Structure):
+    """yuma_scan_plan_t (include/yuma_hip.h): 80 bytes."""
+    _fields_ = [("grid", ctypes.c_longlong)] + [(name, ctypes.c_int32) for name in (
+        "variant", "vector_form", "w_u16", "form", "shape", "rows", "rq", "hs", "hist", "nt", "hist_bf16", "sc",
+        "rowblocks", "cblocks", "block", "ptiles", "dpl", "rc")]
+
+
+assert ctypes.sizeof(YumaScanPlanC) == 80, ctypes.sizeof(YumaScanPlanC)
+
+SCAN_FORMS = ("k_bonds", "k_bonds_cn", "k_rust_big", "k_bonds_elem", "k_bonds_grp")  # YUMA_SCAN_*
+ELEM_SHAPES = (None, "wide", "tile_hist", "tile", "flat1", "flat2")  # YUMA_ELEM_*
+DP_LAYOUTS = ("TV", "VQ", "QTE")  # YUMA_DP_*
+
+
+@dataclass(frozen=True)
+class ScanPlan:
+    """The bond scan a call reaches (yuma_scan_plan_t, names for its enums)."""
+    form: str             # one of SCAN_FORMS
+    shape: str | None     # k_bonds_elem's block shape, one of ELEM_SHAPES
+    rows: int             # rows per lane (k_bonds: per thread)
+    rq: bool              # divides by k_rowsum's screened reciprocals
+    hs: bool              # the strided-history instantiation
+    hist: bool            # writes a history
+    nt: bool              # non-temporal history stores (k_bonds_elem)
+    hist_bf16: bool       # the history's elements are bfloat16
+    sc: bool              # under an input schedule
+    vector_form: bool
+    w_u16: bool
+    rowblocks: int
+    cblocks: int
+    grid: int
+    block: int
+    ptiles: int
+    dpl: str              # one of DP_LAYOUTS
+
+
+def scan_plan(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False, want: tuple[str, ...] = (), *,
+              shared_inputs: bool = False, hist_stride: int = 1, hist_first: int | None = None, w_u16: bool = False,
+              hist_bf16: bool = False, sched: bool = False, vector_form: bool | None = None,
+              shard_stage: bool = False) -> ScanPlan:
+    """The bond scan that `run` with these arguments launches for its first
+    chunk, or (shard_stage) stage 4 of `shard_stage` (yuma_scan_plan; needs the
+    library, not a GPU). The arguments are `run`'s, with w_u16 / hist_bf16 /
+    sched for what `run` takes natively from W.dtype, hist_dtype and sched=;
+    vector_form None is M % 4 == 0 (aligned buffers). EngineError where the
+    engine refuses the combination."""
+    names = {"Dn", "C", "I", "B_final", *want}
+    if want_hist:
+        names.add("B_hist")
+    outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
+    opts = None
+    if not shard_stage:
+        h = hist_epochs(E, hist_stride, hist_first)
+        opts = YumaRunOptionsC(flags=(RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+                               | (RUN_HIST_BF16 if hist_bf16 else 0),
+                               hist_stride=min(int(hist_stride), E), hist_first=h[0] if h else E)
+    p = YumaScanPlanC()
+    vec = M % 4 == 0 if vector_form is None else bool(vector_form)
+    _check(load_library().yuma_scan_plan(variant, N, E, V, M, ctypes.addressof(outs),
+                                         None if opts is None else ctypes.addressof(opts), int(vec), int(sched),
+                                         int(shard_stage), ctypes.addressof(p)), "yuma_scan_plan")
+    return ScanPlan(form=SCAN_FORMS[p.form], shape=ELEM_SHAPES[p.shape], rows=p.rows, rq=bool(p.rq), hs=bool(p.hs),
+                    hist=bool(p.hist), nt=bool(p.nt), hist_bf16=bool(p.hist_bf16), sc=bool(p.sc),
+                    vector_form=bool(p.vector_form), w_u16=bool(p.w_u16), rowblocks=p.rowblocks, cblocks=p.cblocks,
+                    grid=p.grid, block=p.block, ptiles=p.ptiles, dpl=DP_LAYOUTS[p.dpl])
 
 
 def _watch_host(watch, M: int | None, name: str = "watch") -> torch.Tensor:
