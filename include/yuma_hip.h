@@ -357,6 +357,66 @@ int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, i
 int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags);
 
 /* ------------------------------------------------------------------------
+ * Bond movement per epoch: when did the bonds stop moving.
+ *
+ * yuma_run_move writes B_move [E][N][2] (fp32, device memory) beside the
+ * run's other outputs:
+ *   B_move[t][n][0] = max over (v, m) of |B_t[n][v][m] - B_{t-1}[n][v][m]|
+ *   B_move[t][n][1] = max over (v, m) of |B_t[n][v][m]|
+ * B_t is the bond state after epoch t, exactly the bits the dense fp32 history
+ * holds; a reset at epoch t is therefore part of epoch t's movement. B_{-1} is
+ * B_init, or all zeros when B_init is NULL. The difference is one fp32
+ * subtraction and a maximum is order-independent, so the result is
+ * bit-defined: it equals (hist[t] - hist[t-1]).abs().amax((-2, -1)) and
+ * hist[t].abs().amax((-2, -1)) computed in fp32 on the dense history. NaN
+ * propagates as in torch.amax: if any element's |difference| (or |B|) is NaN
+ * the entry is a NaN with unspecified payload. -0 counts as +0. Every other
+ * output, B_final included, keeps the bits of the same run without B_move, and
+ * the result does not depend on chunk_epochs (across a chunk boundary the old
+ * state is the one the scan loads from its state buffer).
+ *
+ * The history-less scan holds every element's old and new state in registers
+ * at the update: it forms the two maxima there, reduces them over the wave and
+ * parks them in LDS; every 256 epochs and at the end of a launch each wave sends
+ * them as unsigned max atomics (one per maximum and epoch); the engine zeroes B_move
+ * itself with a small kernel on the run's stream (inside a captured graph too:
+ * every replay starts from zero). B_move needs no workspace of its own.
+ *
+ * The arguments are yuma_run_watch's with B_move after B_watch. n_watch == 0
+ * with NULL watch_dev and NULL B_watch means "no watch list" (here only:
+ * yuma_run_watch still refuses it).
+ *
+ * Native (yuma_move_native returns 1; host only, makes no HIP call; of `out`
+ * it reads only which pointers are non-NULL; `flags` are the run's flags):
+ * Yuma 3 and Yuma 4 (scalar or liquid alpha, any reset mode), the vector form
+ * (M % 4 == 0, with the alignments YUMA_RUN_W_U16 states), any V up to
+ * YUMA_MAX_VALIDATORS, no YUMA_RUN_SHARED_INPUTS, out->B_hist NULL, none of
+ * Wn / Wc / Wb / B_inst / Tv requested -- the calls whose scan is
+ * YUMA_ELEM_FLAT1 / YUMA_ELEM_FLAT2. Within them it combines with
+ * YUMA_RUN_W_U16 where yuma_u16_native holds (yuma_move_native tests it when
+ * the flag is given), with a schedule where yuma_sched_native holds, and with
+ * a watch list. Elsewhere the entry points return YUMA_EUNSUPPORTED before the
+ * first launch and the caller reduces an fp32 history itself.
+ *
+ * Refusals, in this order, all before the first launch and without a HIP call
+ * (yuma_graph_create_move: the same code and yuma_last_error text, before the
+ * capture opens): the options (as yuma_run_opts); [the graph handle]; sizes;
+ * NULL params / W / S / out / workspace; a schedule pointer with K < 1, or
+ * K != 0 without one (YUMA_EINVAL); with a watch list (n_watch != 0 or either
+ * pointer given), n_watch < 1, then a NULL watch_dev or B_watch (YUMA_EINVAL);
+ * a NULL B_move (YUMA_EINVAL); the workspace size; the schedule not native;
+ * the watch list not native; the movement not native, then not in vector form
+ * (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and YUMA_RUN_W_U16 as ever.
+ * yuma_epoch, yuma_shard_stage and the older entry points take no B_move.
+ * ---------------------------------------------------------------------- */
+int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                  const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                  const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
+                  int n_watch, float* B_watch, float* B_move, void* workspace, size_t workspace_bytes,
+                  int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms);
+int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
+
+/* ------------------------------------------------------------------------
  * Which bond scan a call reaches. Host only, needs no GPU and makes no HIP
  * call: the engine's own choice (the function its runs call before they launch
  * the scan), reported for the first chunk of yuma_run_opts / yuma_run_sched
@@ -458,6 +518,13 @@ int yuma_graph_create_watch(yuma_graph_t* graph, int variant, const yuma_params_
                             const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
                             float* B_watch, void* workspace, size_t workspace_bytes,
                             int chunk_epochs, const yuma_run_options_t* opts);
+/* yuma_graph_create_watch with the bond movement (yuma_run_move's arguments). */
+int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                           int E, int K, int V, int M, const float* W, const float* S,
+                           const int32_t* sched_dev, const float* B_init, const float* Wprev_init,
+                           const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                           float* B_watch, float* B_move, void* workspace, size_t workspace_bytes,
+                           int chunk_epochs, const yuma_run_options_t* opts);
 /* Replay on `stream` (stream-ordered, no host synchronisation). */
 int yuma_graph_launch(yuma_graph_t graph, void* stream);
 /* Kernel nodes in the captured graph (diagnostics / tests). */

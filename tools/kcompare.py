@@ -55,6 +55,11 @@ def kernels(lib, every=False):
 
 
 def key(name):
+    # <..., SC, MV = false> takes ElemArgs<SC, MV>: the name of before the bond movement (MV = true, BondArgsMv /
+    # BondArgsScMv: only in a library that has it)
+    name = re.sub(r"Lb0EEEvNSt11conditionalIXT7_ENS3_IXT6_ENS_12BondArgsScMvENS_10BondArgsMvEE4typeENS3_IXT6_"
+                  r"ENS_10BondArgsScENS_8BondArgsEE4typeEE4typeE$",
+                  "EEvNSt11conditionalIXT6_ENS_10BondArgsScENS_8BondArgsEE4typeE", name)
     # <..., HT, SC = false> takes conditional_t<SC, BondArgsSc, BondArgs>: the name of before the input
     # schedules (SC = true, BondArgsSc: only in a library that has them)
     name = re.sub(r"Lb0EEEvNSt11conditionalIXT\d+_ENS_10BondArgsScENS_8BondArgsEE4typeE$", TAIL, name)

@@ -1029,6 +1029,18 @@ __device__ __forceinline__ int iwmin16(int x) {
   x = min(x, __builtin_amdgcn_mov_dpp(x, 0x140, 0xF, 0xF, false));
   return x;
 }
+// Unsigned maximum over the 64 lanes of a wave, as a wave-uniform value: the
+// 16-lane DPP exchanges above, then one lane of each DPP row read into a scalar
+// (no LDS crossbar, so nothing for lgkmcnt to wait on).
+__device__ __forceinline__ unsigned uwmax64(unsigned x) {
+  x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0xB1, 0xF, 0xF, false));
+  x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x4E, 0xF, 0xF, false));
+  x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x141, 0xF, 0xF, false));
+  x = max(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, 0x140, 0xF, 0xF, false));
+  const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)x, 0), b = (unsigned)__builtin_amdgcn_readlane((int)x, 16);
+  const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)x, 32), d = (unsigned)__builtin_amdgcn_readlane((int)x, 48);
+  return max(max(a, b), max(c, d));
+}
 // Exclusive prefix sum over the 16 lanes of a DPP row (row_shr:1,2,4,8 with
 // bound_ctrl: lanes shifted in from outside the row read 0).
 __device__ __forceinline__ int iscan16_excl(int x) {
@@ -3260,6 +3272,16 @@ struct BondArgsSc : BondArgs {
   const int32_t* sched;  // [E] device memory: epoch t reads stored slice sched[t]
   int K;                 // stored slices
 };
+// ... with the per-epoch bond movement (k_bonds_elem<.., MV = true>), and both
+struct BondArgsMv : BondArgs {
+  float* B_move;  // [E][N][2], zeroed before the run's first scan (k_move_zero)
+};
+struct BondArgsScMv : BondArgsSc {
+  float* B_move;
+};
+template <bool SC, bool MV>
+using ElemArgs = std::conditional_t<MV, std::conditional_t<SC, BondArgsScMv, BondArgsMv>,
+                                    std::conditional_t<SC, BondArgsSc, BondArgs>>;
 __host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
   return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
 }
@@ -4072,6 +4094,24 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // no fetch waits for it. BondArgs has no room for the two words: the SC
 // instantiations take BondArgsSc, the record with the two appended, and every
 // other instantiation keeps its argument block and its code.
+// MV: the per-epoch bond movement (yuma_run_move). B_move[t][n][0] is the
+// maximum over (v, m) of |B_t - B_{t-1}|, B_move[t][n][1] that of |B_t|, B_t
+// the state after epoch t (the bits a dense fp32 history holds; a reset at
+// epoch t is part of epoch t's movement; B_{-1} is B_init or zeros; across a
+// chunk boundary the old state is the one loaded from Bstate). Each lane keeps
+// the row's four old values past the update, takes |x| of the fp32 difference
+// and of the new state as a bit mask (-0 counts as +0), and reduces them as
+// unsigned integers: for non-negative floats the unsigned order is the float
+// order and every NaN pattern lies above +inf, so a NaN wins the maximum as in
+// torch.amax. Rows >= V and quads >= M contribute 0. After a wave reduction
+// (uwmax64) the wave parks the two maxima in LDS (mbuf, as qbuf parks the quad
+// partials) and sends them, behind the unrolled epoch bodies, when the buffer
+// is full or the launch ends: one
+// returnless unsigned max atomic per maximum, wave and epoch, to B_move,
+// which the engine has zeroed (k_move_zero). A maximum is order-
+// independent, so the result is bit-defined. The MV instantiations take
+// BondArgsMv / BondArgsScMv, the records with the pointer appended; every
+// other instantiation keeps its argument block and its code.
 // SH: the block shape, an ElemShape (R, P, BS, CB as above; VECI: float4
 // incentive / bond_alpha loads; NT: non-temporal history stores; DPL: the
 // dividend-partial layout).
@@ -4081,10 +4121,12 @@ struct ElemShape {
   static constexpr bool VECI = VECI_, NT = NT_;
 };
 template <int VARIANT, typename SH, bool VEC, bool RQ = false, typename WT = float, bool HS = false,
-          typename HT = float, bool SC = false>
-__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC, BondArgsSc, BondArgs> A) {
+          typename HT = float, bool SC = false, bool MV = false>
+__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV> A) {
   constexpr int R = SH::R, P = SH::P, BS = SH::BS, CB = SH::CB, DPL = SH::DPL;
   constexpr bool VECI = SH::VECI, NT = SH::NT;
+  static_assert(!MV || (VEC && DPL == DP_QTE && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<HT, float> && !HS),
+                "bond movement: Yuma 3 / Yuma 4, vector form, the history-less flat shapes");
   static_assert(!SC || (VEC && VARIANT >= YUMA_VARIANT_YUMA3), "input schedules: Yuma 3 / Yuma 4, vector form");
   static_assert(std::is_same_v<HT, float> || (std::is_same_v<HT, __bf16> && NT && VEC && !RQ &&
                                               VARIANT >= YUMA_VARIANT_YUMA3),
@@ -4184,6 +4226,9 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC,
   constexpr int kQBuf = 256, NWB = BS / 64;
   __shared__ float qbuf[DPL == DP_QTE ? NWB * R * kQBuf : 1];
   int tq = A.t0;  // first epoch held in qbuf
+  // MV: each wave's two maxima of up to kQBuf epochs, parked and sent like the quad partials
+  __shared__ unsigned mbuf[MV ? NWB * 2 * kQBuf : 1];
+  [[maybe_unused]] int tm = A.t0;  // first epoch held in mbuf
   // a duplicate scenario of a rank class reads its representative's column sums
   // (the rank pass skips duplicate slices; k_incentive copies R, not csb / csr)
   const int ncs = (COLNORM && A.csrep != nullptr) ? A.csrep[n] : n;
@@ -4255,17 +4300,28 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC,
       // store this epoch's state? Block-uniform, from t alone (never a lane's
       // branch: see the dividend sum below for what those cost here)
       const bool hst = HS && t == hnext;
+      // MV: the reset is applied row by row below, after the row's old values
+      // are set aside (rfire: this lane resets; rcol: its column of the quad)
+      [[maybe_unused]] bool rfire = false;
+      [[maybe_unused]] int rcol = 0;
+      [[maybe_unused]] unsigned mvd = 0u, mvb = 0u;  // MV: this lane's max |B_t - B_{t-1}| and max |B_t|, as bits
       if (!COLNORM && has_old && reset_mode != YUMA_RESET_NONE && t == reset_epoch &&
           (reset_all || (reset_index >= 0 && reset_index < M))) {
         bool fire = reset_mode == YUMA_RESET_ALWAYS;
         if (reset_mode == YUMA_RESET_IF_ZERO_CONSENSUS && t >= 1 && !reset_all) fire = zero_c;
         const int c = reset_index - m;
-        if (fire && (reset_all || (c >= 0 && c < 4)))
+        if (fire && (reset_all || (c >= 0 && c < 4))) {
+          if constexpr (MV) {
+            rfire = true;
+            rcol = c;
+          } else {
 #pragma unroll
-          for (int i = 0; i < R; ++i)
+            for (int i = 0; i < R; ++i)
 #pragma unroll
-            for (int cc = 0; cc < 4; ++cc)
-              if (reset_all || cc == c) B[i][cc] = 0.0f;
+              for (int cc = 0; cc < 4; ++cc)
+                if (reset_all || cc == c) B[i][cc] = 0.0f;
+          }
+        }
       }
       float bac[4], omba[4];
 #pragma unroll
@@ -4300,6 +4356,14 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC,
         constexpr bool SHORT = !COLNORM && !(VARIANT == YUMA_VARIANT_YUMA4 && NT);
         auto mn = [](float a, float b) { return SHORT ? vmin(a, b) : tmin(a, b); };
         auto mx = [](float a, float b) { return SHORT ? vmax(a, b) : tmax(a, b); };
+        [[maybe_unused]] float old[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (MV) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            old[c] = B[i][c];
+            if (rfire && (reset_all || c == rcol)) B[i][c] = 0.0f;
+          }
+        }
         // (k_rowsum's screened reciprocal instead of the per-row one and the
         // per-element guard: c2 wide history scan 1.58 -> 1.70 ms, c4 1.63 ->
         // 1.73, same box; kept only in the issue-bound sweep scan k_bonds_grp)
@@ -4385,6 +4449,17 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC,
             B[i][c] = mn(nb, 1.0f);
           }
         }
+        if constexpr (MV) {
+          // M % 4 == 0: the quad is wholly in or out. A select, never a lane's branch
+          const bool in = row < V && m < M;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const unsigned d = __builtin_bit_cast(unsigned, B[i][c] - old[c]) & 0x7fffffffu;
+            const unsigned a = __builtin_bit_cast(unsigned, B[i][c]) & 0x7fffffffu;
+            mvd = max(mvd, in ? d : 0u);
+            mvb = max(mvb, in ? a : 0u);
+          }
+        }
         if ((HS ? hst : A.B_hist != nullptr) && row < V) {
           if constexpr (std::is_same_v<HT, float>) {
             float* hp = A.B_hist + (HS ? hsl : slice) * VM + (long long)row * M;
@@ -4448,6 +4523,19 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC,
           A.dpart[dp_index(slice, tile, row, A.tiles, V)] = d;
         }
       }
+      if constexpr (MV) {
+        // the wave's two maxima, parked in LDS like the quad partials; they are
+        // sent behind the unrolled epoch bodies (below), none from inside them.
+        // (Two atomics issued here at every epoch, or a flush block in every
+        // body, made the compiler wait vmcnt(0) twice per epoch, draining the
+        // prefetch ring: DESIGN.md section 13.)
+        const unsigned wd = uwmax64(mvd), wb = uwmax64(mvb);
+        unsigned* mb = mbuf + (threadIdx.x >> 6) * 2 * kQBuf;
+        if (lane == 0) {
+          mb[t - tm] = wd;
+          mb[kQBuf + t - tm] = wb;
+        }
+      }
       if (HS && hst) {
         hnext += A.hstride;
         hsl += N;
@@ -4459,12 +4547,43 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SC,
         if constexpr (SC) snext = sched_at(t + P + 1);
       }
     }
+    if constexpr (MV) {
+      // MV: send the parked maxima when the buffer is full (P divides kQBuf) or
+      // the launch ends: one returnless atomic per maximum, wave and epoch
+      // (relaxed, result unused), 64 epochs to an instruction
+      static_assert(kQBuf % P == 0, "the parking buffer fills at the end of a pass over the P bodies");
+      const int td = min(tb + P, A.t1);  // epochs [tm, td) are parked; wave-uniform
+      if (td - tm == kQBuf || td == A.t1) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const unsigned* mb = mbuf + (threadIdx.x >> 6) * 2 * kQBuf;
+        unsigned* mp = reinterpret_cast<unsigned*>(A.B_move) + ((long long)tm * N + n) * 2;
+        for (int e = lane; e < td - tm; e += 64) {
+          (void)__hip_atomic_fetch_max(mp + (long long)e * N * 2, mb[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          (void)__hip_atomic_fetch_max(mp + (long long)e * N * 2 + 1, mb[kQBuf + e], __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        tm = td;
+      }
+    }
   }
 #pragma unroll
   for (int i = 0; i < R; ++i) {
     const int row = row0 + G * i;
     if (row < V) store4<VEC>(A.Bstate + n * VM + (long long)row * M, m, M, B[i]);
   }
+}
+
+// Bond movement (yuma_run_move): B_move's E N 2 words to +0 before the run's
+// first scan, whose unsigned max atomics start from it. A kernel, not a memset
+// node: a captured run stays a chain of kernel nodes, and every replay starts
+// from zero.
+__global__ __launch_bounds__(256) void k_move_zero(float* p, long long n) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = 0.0f;
 }
 
 // ---------------------------------------------------------------------------
@@ -5805,8 +5924,13 @@ struct ScanKey {
   bool rq;       // k_rowsum's screened reciprocals at hand (rq4: a run has them, a shard stage does not)
   bool csb;      // the rank pass formed the bond column sums (forms_csb)
   bool full;     // W_b or the instantaneous bonds requested
+  bool mv;       // the per-epoch bond movement (yuma_run_move; move_native holds)
 };
-using ScanPlan = yuma_scan_plan_t;
+// yuma_scan_plan_t as yuma_scan_plan reports it, and the movement choice
+// (the MV instantiation of the flat shape) beside it
+struct ScanPlan : yuma_scan_plan_t {
+  int mv;
+};
 
 // The scan of a chunk: its kernel, that kernel's flags, the grid, and the
 // layout and granularity (ptiles: partials per slice and validator) of the
@@ -5837,6 +5961,7 @@ ScanPlan plan_scan(const ScanKey& k) {
   p.rc = k.rc;
   p.ptiles = tiles;
   p.dpl = yk::DP_TV;
+  p.mv = k.mv;  // (move_native: the key reaches the flat shapes below; launch_scan refuses any other)
   // a kernel of `block` threads whose blocks own brows rows x bcols miners of `per` scenarios
   auto plan = [&](int form, int rows, int block, int brows, int bcols, bool rq, int per = 1) {
     p.form = form;
@@ -5901,7 +6026,8 @@ ScanPlan plan_scan(const ScanKey& k) {
 // (Defined behind shard_stage_impl, the first caller in the file: the scans are
 // instantiated where launch_scan is defined, and so keep their place in the
 // code object, behind the kernels of phase 1.)
-void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K);
+void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K,
+                 float* B_move = nullptr);
 
 // The watched columns' scan over the chunk of A (k_bonds_watch), from the main
 // scan's own arguments: the same inputs, state and history countdown. Enqueued
@@ -6012,6 +6138,22 @@ bool watch_native(int variant, int N, int E, int V, int M, int n_watch, int flag
   if (N < 1 || E < 1 || V < 1 || M < 1 || n_watch < 1 || V > YUMA_MAX_VALIDATORS) return false;
   if (flags & YUMA_RUN_SHARED_INPUTS) return false;
   if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, nullptr, flags)) return false;
+  return true;
+}
+
+// Whether a run with these arguments forms the per-epoch bond movement inside
+// its scan (yuma_move_native): exactly the calls plan_scan sends to the flat
+// history-less shapes -- the element-wise variants in vector form, any
+// validator count, per-scenario inputs, no history and none of the per-epoch
+// matrices requested. Only those shapes are instantiated with MV. With
+// YUMA_RUN_W_U16 in `flags`, where the uint16 weights are native. (An input
+// schedule in the same run: where yuma_sched_native holds as well.)
+bool move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || V < 1 || M < 1 || V > YUMA_MAX_VALIDATORS || (M % 4) != 0) return false;
+  if (flags & (YUMA_RUN_SHARED_INPUTS | YUMA_RUN_HIST_BF16)) return false;
+  if (out != nullptr && (out->B_hist || out->Wn || out->Wc || out->Wb || out->B_inst || out->Tv)) return false;
+  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags)) return false;
   return true;
 }
 
@@ -6142,6 +6284,10 @@ struct RunReq {
   const int32_t* watch = nullptr;
   int n_watch = 0;
   float* B_watch = nullptr;
+  // yuma_run_move (has_move): the per-epoch bond movement B_move [E][N][2]; its watch list may be empty
+  // (n_watch = 0 with NULL watch / B_watch: has_watch stays 0)
+  int has_move = 0;
+  float* B_move = nullptr;
 };
 
 // The history countdown (BondArgs::hnext) of the chunk from epoch A.t0 of the
@@ -6176,6 +6322,7 @@ ScanKey scan_key(const RunReq& q, bool vec, bool sched, bool run, bool strided) 
   k.rq = run;
   k.csb = forms_csb(q.variant, q.V, q.out);
   k.full = q.out->Wb != nullptr || q.out->B_inst != nullptr;
+  k.mv = q.has_move != 0;
   return k;
 }
 
@@ -6212,6 +6359,18 @@ int check_native(const RunReq& q, bool vec, bool sched, int K) {
                 "a watch list is not native for variant=%d V=%d shared=%d (yuma_watch_native): run the fp32 "
                 "history and gather the columns",
                 variant, V, wsh);
+  if (q.has_move) {
+    const int f = (wsh ? YUMA_RUN_SHARED_INPUTS : 0) | (q.w_u16 ? YUMA_RUN_W_U16 : 0) | (q.hist_bf16 ? YUMA_RUN_HIST_BF16 : 0);
+    if (!move_native(variant, N, E, V, M, out, f))
+      return fail(YUMA_EUNSUPPORTED,
+                  "the bond movement is not native for variant=%d V=%d M=%d flags=0x%x or the requested outputs "
+                  "(yuma_move_native): run the fp32 history and reduce it",
+                  variant, V, M, f);
+    if (!vec)
+      return fail(YUMA_EUNSUPPORTED,
+                  "the bond movement (yuma_move_native) needs the vector form: W vector-aligned and the fp32 "
+                  "matrices 16-byte aligned");
+  }
   if (q.hist_bf16) {
     if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
     if (!hist_bf16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
@@ -6273,6 +6432,7 @@ int run_plan(const RunReq& q, RunPlan* p) {
     if (((long long)V * q.n_watch + yk::kWatchBS - 1) / yk::kWatchBS * N > INT_MAX)
       return fail(YUMA_EINVAL, "n_watch=%d: N V n_watch elements exceed the watch kernel's grid", q.n_watch);
   }
+  if (q.has_move && q.B_move == nullptr) return fail(YUMA_EINVAL, "B_move is NULL");
   const int full = out->Tv != nullptr;
   // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
   // params live in device memory, so the Python marshaller enforces it.
@@ -6442,6 +6602,10 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     YK_LAUNCH(yk::k_sched_expand, (long long)E * N * na, 256, st, X);
   }
 
+  if (q.has_move) {  // before the first chunk's scan; every chunk's atomics add to it
+    const long long nm = (long long)E * N * 2;
+    YK_LAUNCH(yk::k_move_zero, (nm + 255) / 256 < 1024 ? (nm + 255) / 256 : 1024, 256, st, q.B_move, nm);
+  }
   for (int c0 = 0; c0 < E; c0 += chunk) {
     const int c1 = c0 + chunk < E ? c0 + chunk : E;
     const long long s0 = (long long)c0 * N;
@@ -6462,7 +6626,7 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     if (q.has_watch)  // (Yuma 3 / Yuma 4: run_plan) the state before epoch c0 is still in A.Bstate
       launch_watch<WT>(st, variant, A, q.watch, q.n_watch, q.B_watch, sched, K);
     const ScanPlan scan = plan_scan(scan_key(q, vec, sched != nullptr, true, yk::hist_strided(A)));
-    launch_scan(st, scan, A, sched, K);
+    launch_scan(st, scan, A, sched, K, q.B_move);
     const int ptiles = scan.ptiles;
     int dpl = scan.dpl;
     tm.mark(YUMA_PHASE_FINALIZE);
@@ -6654,7 +6818,7 @@ using Mode = std::integral_constant<int, MODE>;
 // written at each kernel are the instantiated set, in this one place; any
 // other plan aborts (bad_plan).
 template <int VARIANT, bool VEC, typename WT, bool SC>
-void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K) {
+void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move) {
   constexpr bool kPlain = std::is_same_v<WT, float> && !SC;  // fp32 W, no schedule
   constexpr bool kColnorm = VARIANT <= YUMA_VARIANT_YUMA2, kElem34 = VARIANT >= YUMA_VARIANT_YUMA3;
   const long long nb = p.grid;
@@ -6726,21 +6890,27 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
     // k_bonds_elem in the shape sh, with the plan's RQ, HS and bfloat16 history where
     // the modes admit them. sched (with SC): the input schedule and its K
     // stored slices (BondArgsSc)
-    auto elem = [&](auto sh, auto rq_mode, auto hs_mode, auto bf16_mode) {
+    // mv_mode: the bond movement (B_move; BondArgsMv / BondArgsScMv), on the
+    // flat shapes of Yuma 3 / Yuma 4 in vector form only, and there with the
+    // screened reciprocal always (a run has it: plan_scan) and no history
+    auto elem = [&](auto sh, auto rq_mode, auto hs_mode, auto bf16_mode, auto mv_mode) {
       using SH = decltype(sh);
-      with_flag<decltype(rq_mode)::value>(p, p.rq, [&](auto RQ) {
-        with_flag<decltype(hs_mode)::value>(p, p.hs, [&](auto HS) {
-          with_flag<decltype(bf16_mode)::value>(p, p.hist_bf16, [&](auto BF16) {
-            using HT = std::conditional_t<decltype(BF16)::value, __bf16, float>;
-            constexpr bool kRq = decltype(RQ)::value, kHs = decltype(HS)::value;
-            if constexpr (SC) {
-              yk::BondArgsSc As{};
+      with_flag<decltype(mv_mode)::value>(p, p.mv, [&](auto MV) {
+        constexpr bool kMv = decltype(MV)::value;
+        with_flag<(kMv ? kAlways : decltype(rq_mode)::value)>(p, p.rq, [&](auto RQ) {
+          with_flag<(kMv ? kNever : decltype(hs_mode)::value)>(p, p.hs, [&](auto HS) {
+            with_flag<(kMv ? kNever : decltype(bf16_mode)::value)>(p, p.hist_bf16, [&](auto BF16) {
+              using HT = std::conditional_t<decltype(BF16)::value, __bf16, float>;
+              constexpr bool kRq = decltype(RQ)::value, kHs = decltype(HS)::value;
+              yk::ElemArgs<SC, kMv> As{};
               static_cast<yk::BondArgs&>(As) = A;
-              As.sched = sched;
-              As.K = K;
-              YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, VEC, kRq, WT, kHs, HT, true>), nb, SH::BS, st, As);
-            } else
-              YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, VEC, kRq, WT, kHs, HT>), nb, SH::BS, st, A);
+              if constexpr (SC) {
+                As.sched = sched;
+                As.K = K;
+              }
+              if constexpr (kMv) As.B_move = B_move;
+              YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, VEC, kRq, WT, kHs, HT, SC, kMv>), nb, SH::BS, st, As);
+            });
           });
         });
       });
@@ -6749,22 +6919,23 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
     // from them; vector form: no history, RQ as planned, under a schedule always
     constexpr Mode<(!VEC ? kNever : SC ? kAlways : kEither)> flat_rq{};
     constexpr Mode<(kElem34 && VEC ? kEither : kNever)> bf16{};  // bfloat16: Yuma 3 / Yuma 4 in vector form
+    constexpr Mode<(kElem34 && VEC ? kEither : kNever)> flat_mv{};  // the bond movement: the flat shapes of those
     constexpr Mode<kNever> never{};
     constexpr Mode<kEither> either{};
     if (p.form == YUMA_SCAN_ELEM) switch (p.shape) {
         case YUMA_ELEM_WIDE:  // vector form; RQ for Yuma / Yuma2 (kElemRq)
           if constexpr (VEC)
-            return elem(ElemWide<VARIANT>{}, Mode<(kElemRq(VARIANT, true) ? kEither : kNever)>{}, either, bf16);
+            return elem(ElemWide<VARIANT>{}, Mode<(kElemRq(VARIANT, true) ? kEither : kNever)>{}, either, bf16, never);
           break;
         case YUMA_ELEM_TILE_HIST:
-          return elem(ElemTileHist<VEC>{}, never, either, bf16);
+          return elem(ElemTileHist<VEC>{}, never, either, bf16, never);
         case YUMA_ELEM_TILE:  // no schedule
-          if constexpr (!SC) return elem(ElemTile<VEC>{}, never, never, never);
+          if constexpr (!SC) return elem(ElemTile<VEC>{}, never, never, never, never);
           break;
         case YUMA_ELEM_FLAT1:
-          return elem(ElemFlat1<VEC>{}, flat_rq, Mode<(VEC ? kNever : kEither)>{}, never);
+          return elem(ElemFlat1<VEC>{}, flat_rq, Mode<(VEC ? kNever : kEither)>{}, never, flat_mv);
         case YUMA_ELEM_FLAT2:
-          return elem(ElemFlat2<VEC>{}, flat_rq, Mode<(VEC ? kNever : kEither)>{}, never);
+          return elem(ElemFlat2<VEC>{}, flat_rq, Mode<(VEC ? kNever : kEither)>{}, never, flat_mv);
       }
   }
   bad_plan(p);
@@ -6773,22 +6944,22 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
 // Launch the bond scan that plan_scan chose, for A.N scenarios over epochs
 // [A.t0, A.t1): the only place a bond scan is instantiated. uint16 weights
 // and input schedules are Yuma 3 / Yuma 4 in vector form (run_plan).
-void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K) {
+void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move) {
   A.rowblocks = p.rowblocks;
   A.cblocks = p.cblocks;
-  if ((p.rq && A.rq4 == nullptr) || (p.sc && sched == nullptr)) bad_plan(p);
+  if ((p.rq && A.rq4 == nullptr) || (p.sc && sched == nullptr) || (p.mv != 0) != (B_move != nullptr)) bad_plan(p);
   with_variant(p.variant, [&](auto VARIANT) {
     constexpr int kVariant = decltype(VARIANT)::value;
     if constexpr (kVariant >= YUMA_VARIANT_YUMA3) {
       if (p.vector_form && p.w_u16)
         return with_bool(p.sc != 0, [&](auto SC) {
-          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K);
+          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K, B_move);
         });
-      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K);
+      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K, B_move);
     }
     if (p.w_u16 || p.sc) bad_plan(p);
     with_bool(p.vector_form != 0, [&](auto VEC) {
-      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K);
+      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K, B_move);
     });
   });
 }
@@ -6833,6 +7004,16 @@ void read_watch(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n
   q->watch = watch_dev;
   q->n_watch = n_watch;
   q->B_watch = B_watch;
+}
+
+// yuma_run_move / yuma_graph_create_move: as read_watch, but n_watch = 0 with NULL watch_dev and B_watch is
+// "no watch list"; and the movement output as given (run_plan refuses a NULL one).
+void read_move(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
+               RunReq* q) {
+  read_watch(sched_dev, K, watch_dev, n_watch, B_watch, q);
+  if (n_watch == 0 && watch_dev == nullptr && B_watch == nullptr) q->has_watch = 0;
+  q->has_move = 1;
+  q->B_move = B_move;
 }
 
 // A direct run: validate, then enqueue on the caller's stream, in the weight type the request names.
@@ -6948,6 +7129,22 @@ int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, i
   if (const int err = read_opts(opts, &q)) return err;
   read_watch(sched_dev, K, watch_dev, n_watch, B_watch, &q);
   return run_direct(q);
+}
+
+int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                  const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                  const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                  float* B_watch, float* B_move, void* workspace, size_t workspace_bytes, int chunk_epochs,
+                  const yuma_run_options_t* opts, void* stream, float* phase_ms) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, &q);
+  return run_direct(q);
+}
+
+int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  return move_native(variant, N, E, V, M, out, flags) ? 1 : 0;
 }
 
 int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags) {
@@ -7068,6 +7265,18 @@ int yuma_graph_create_watch(yuma_graph_t* graph, int variant, const yuma_params_
            chunk_epochs, nullptr, nullptr};
   if (const int err = read_opts(opts, &q)) return err;
   read_watch(sched_dev, K, watch_dev, n_watch, B_watch, &q);
+  return graph_create_impl(graph, q);
+}
+
+int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
+                           int K, int V, int M, const float* W, const float* S, const int32_t* sched_dev,
+                           const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                           const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move, void* workspace,
+                           size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, &q);
   return graph_create_impl(graph, q);
 }
 

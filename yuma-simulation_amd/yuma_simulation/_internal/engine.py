@@ -54,6 +54,9 @@ EXPORTED_SYMBOLS = (
     "yuma_run_watch",
     "yuma_watch_native",
     "yuma_graph_create_watch",
+    "yuma_run_move",
+    "yuma_move_native",
+    "yuma_graph_create_move",
     "yuma_scan_plan",
     "yuma_epoch",
     "yuma_synth_weights",
@@ -231,6 +234,16 @@ def load_library(path: str | None = None):
             lib.yuma_graph_create_watch.restype = i32
             lib.yuma_watch_native.argtypes = [i32, i32, i32, i32, i32, i32, i32]
             lib.yuma_watch_native.restype = i32
+        # bond movement: yuma_run_watch's arguments with B_move after B_watch
+        if hasattr(lib, "yuma_run_move"):  # (A/B libraries of older sources lack them)
+            a = lib.yuma_run_watch.argtypes
+            lib.yuma_run_move.argtypes = a[:16] + [vp] + a[16:]
+            lib.yuma_run_move.restype = i32
+            a = lib.yuma_graph_create_watch.argtypes
+            lib.yuma_graph_create_move.argtypes = a[:17] + [vp] + a[17:]
+            lib.yuma_graph_create_move.restype = i32
+            lib.yuma_move_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
+            lib.yuma_move_native.restype = i32
         if hasattr(lib, "yuma_scan_plan"):  # (A/B libraries of older sources lack it)
             lib.yuma_scan_plan.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp]
             lib.yuma_scan_plan.restype = i32
@@ -499,6 +512,7 @@ class RunResult:
     hist_epochs: tuple[int, ...] | None = None  # the epoch each B_hist / B_watch slice holds (None: neither)
     B_watch: torch.Tensor | None = None         # [len(hist_epochs), N, V, len(watch_cols)] (run(watch=))
     watch_cols: tuple[int, ...] | None = None   # the miner column of each B_watch column
+    B_move: torch.Tensor | None = None          # [E, N, 2]: max |B_t - B_{t-1}|, max |B_t| (run(want_move=True))
 
 
 def _as_dev(x: torch.Tensor, dev) -> torch.Tensor:
@@ -563,6 +577,58 @@ def watch_native(variant: int, N: int, E: int, V: int, M: int, n_watch: int, *, 
     `run` writes an fp32 history and gathers the columns, and RunGraph refuses."""
     flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
     return bool(load_library().yuma_watch_native(variant, N, E, V, M, n_watch, flags))
+
+
+def move_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False,
+                want: tuple[str, ...] = (), *, shared_inputs: bool = False, w_u16: bool = False) -> bool:
+    """Whether `run(..., want_move=True)` with these arguments has the bond scan
+    form B_move itself (yuma_move_native; needs the library, not a GPU): Yuma 3
+    / Yuma 4, any V, M % 4 == 0, no shared inputs, no history and none of Wn /
+    Wc / Wb / B_inst / Tv wanted; with w_u16, where u16_native holds too.
+    Otherwise `run` reduces a dense fp32 history and RunGraph refuses."""
+    names = {"Dn", "C", "I", "B_final", *want}
+    if want_hist:
+        names.add("B_hist")
+    outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
+    flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+    return bool(load_library().yuma_move_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
+
+
+def move_from_history(hist: torch.Tensor, B_init: torch.Tensor | None) -> torch.Tensor:
+    """B_move [E, N, 2] of a dense fp32 history [E, N, V, M], by the two
+    expressions that define it: (hist[t] - hist[t-1]).abs().amax((-2, -1)) and
+    hist[t].abs().amax((-2, -1)), hist[-1] being B_init or zeros. A block of
+    epochs at a time, so that the temporaries stay small beside the history."""
+    E, N, V, M = hist.shape
+    out = torch.empty((E, N, 2), dtype=torch.float32, device=hist.device)
+    first = torch.zeros((1, N, V, M), dtype=torch.float32, device=hist.device) if B_init is None else B_init[None]
+    step = max(1, (1 << 26) // max(1, N * V * M))
+    for t0 in range(0, E, step):
+        cur = hist[t0:t0 + step]
+        prev = torch.cat([first if t0 == 0 else hist[t0 - 1:t0], cur[:-1]])
+        out[t0:t0 + step, :, 0] = (cur - prev).abs().amax((-2, -1))
+        out[t0:t0 + step, :, 1] = cur.abs().amax((-2, -1))
+    return out
+
+
+def settled_epoch(B_move, tol: float, *, relative: bool = False) -> torch.Tensor:
+    """When the bonds stopped moving. B_move is [E, ..., 2] (a RunResult's
+    [E, N, 2], or one run's [E, 2]; torch or numpy, on any device): for every
+    leading index n the first epoch t with B_move[t', n, 0] <= tol for every
+    t' >= t, or (relative) B_move[t', n, 0] <= tol * B_move[t', n, 1] -- the
+    form Yuma 3 needs, whose bonds carry the 2^64 maxint scale. E where no such
+    t exists; a NaN entry never counts as settled. Returns a CPU int64 tensor
+    of shape B_move.shape[1:-1]. Pure torch: needs neither the library nor a
+    GPU."""
+    b = torch.as_tensor(B_move).detach().to("cpu")
+    if b.dim() < 2 or b.shape[-1] != 2:
+        raise ValueError(f"B_move shape {tuple(b.shape)} is not [E, ..., 2]")
+    moved, size = b[..., 0], b[..., 1]
+    ok = moved <= (tol * size if relative else tol)  # (a NaN on either side compares false)
+    E = b.shape[0]
+    idx = torch.arange(E, dtype=torch.int64).reshape((E,) + (1,) * (ok.dim() - 1))
+    last_bad = torch.where(~ok, idx, torch.full_like(idx, -1)).amax(0) if E else torch.full(ok.shape[1:], -1)
+    return (last_bad + 1).to(torch.int64)
 
 
 class YumaScanPlanC(ctypes.Structure):
@@ -773,7 +839,7 @@ def _vector_form(W: torch.Tensor, w_u16: bool, B_init, Wprev_init, o: dict, hist
 
 
 def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_inputs, hist_stride, hist_first,
-                hist_dtype, sched, watch=None):
+                hist_dtype, sched, watch=None, want_move=False):
     """run's argument checks, in the order run has always raised them: the
     history type and the schedule before anything touches a GPU, the rest
     behind device(). Returns (dev, N, E, K, sched_host, h_epochs, watch_host);
@@ -783,6 +849,10 @@ def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_in
         raise ValueError(f"hist_dtype={hist_dtype} must be None, torch.float32 or torch.bfloat16")
     if hist_dtype == torch.bfloat16 and single_call:
         raise ValueError("single_call (yuma_epoch) writes an fp32 history: no hist_dtype=torch.bfloat16")
+    if not isinstance(want_move, (bool, np.bool_)):
+        raise ValueError(f"want_move must be a bool, not {type(want_move).__name__}")
+    if want_move and single_call:
+        raise ValueError("single_call (yuma_epoch) takes no B_move: no want_move")
     E, Nw, V, M = W.shape
     K = sched_host = None
     if sched is not None:  # validated before anything touches a GPU
@@ -843,13 +913,19 @@ _OUT_SHAPES = {
 }
 
 
-def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None) -> None:
+def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None, move=None) -> None:
     """The run's one launch: yuma_run_opts, yuma_run_sched under a native
     schedule, or yuma_run_watch with a native watch list (watch: the int32
     device list, B_watch and the buffer whose address the engine gets); with `capture`, their yuma_graph_create_* twins,
     the handle appended to it. head: variant, params, N, E; tail: V, M ...
-    chunk_epochs."""
-    if watch is not None:  # yuma_run_sched's arguments (no schedule: NULL, K = 0), the list after `out`
+    chunk_epochs. move: B_move, for yuma_run_move (its watch list may be
+    absent: NULL, 0, NULL)."""
+    if move is not None:  # yuma_run_watch's arguments, B_move after B_watch
+        run_fn, graph_fn = lib.yuma_run_move, lib.yuma_graph_create_move
+        w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
+        args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
+                + w + (move.data_ptr(),) + tail[7:])
+    elif watch is not None:  # yuma_run_sched's arguments (no schedule: NULL, K = 0), the list after `out`
         run_fn, graph_fn = lib.yuma_run_watch, lib.yuma_graph_create_watch
         args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
                 + (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr()) + tail[7:])
@@ -879,7 +955,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
         hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None,
-        watch=None) -> RunResult:
+        watch=None, want_move: bool = False) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -927,13 +1003,69 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     2, shared inputs, single_call) the run writes an fp32 history, the columns
     are gathered from it on the device and the dense history is dropped unless
     asked for (extra["watch_path"] == "dense"; a captured run raises
-    EngineError instead)."""
+    EngineError instead).
+    want_move: the result's B_move [E, N, 2] (fp32, on the device) holds per
+    epoch and scenario max over (v, m) of |B_t - B_{t-1}| and of |B_t|, B_t the
+    bond state after epoch t with the dense fp32 history's bits (a reset at
+    epoch t is part of epoch t's movement; B_{-1} is B_init or zeros): bit-equal
+    to (hist[t] - hist[t-1]).abs().amax((-2, -1)) and hist[t].abs().amax((-2,
+    -1)) on that history, NaN as in torch.amax, independent of chunk_epochs;
+    every other output keeps its bits (settled_epoch reads it). Where
+    move_native holds (and the buffers have the vector form's alignment) the
+    history-less scan forms it in registers (yuma_run_move, extra["move_path"]
+    == "native"); elsewhere (Yuma 0 / 1 / 2, shared inputs, the scalar form, a
+    history requested in the same run) the run writes a dense fp32 history,
+    B_move is reduced from it on the device, a requested strided and / or
+    bfloat16 history is taken from it, and it is dropped unless asked for
+    (extra["move_path"] == "dense"; a captured run raises EngineError
+    instead)."""
     h_bf16 = hist_dtype == torch.bfloat16
     dev, N, E, K, sched_host, h_epochs, watch_host = _check_args(
         params, W, S, B_init, Wprev_init, out, single_call=single_call, shared_inputs=shared_inputs,
-        hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched, watch=watch)
+        hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched, watch=watch,
+        want_move=want_move)
     V, M = W.shape[2:]
     lib = load_library()
+    W_arg, S_arg = W, S  # as given: the code below rebinds W and S (widened, moved, expanded under a schedule)
+
+    def move_dense():
+        """B_move from a dense fp32 history of the same run, on the inputs and
+        the schedule as the caller gave them; the history asked for (its stride,
+        its type, the caller's buffer) and B_watch from it."""
+        if capture is not None:
+            raise EngineError("a captured run cannot reduce a dense history: want_move needs "
+                              "move_native(variant, N, E, V, M, ...), no history in the same run and "
+                              "vector-aligned buffers")
+        o_in = {k: v for k, v in (out or {}).items() if k != "B_hist"}
+        r = run(variant, params, W_arg, S_arg, B_init, Wprev_init, want_hist=True, want=want, chunk_epochs=chunk_epochs,
+                workspace=workspace, out=o_in or None, phase_ms=phase_ms, shared_inputs=shared_inputs, sched=sched)
+        dense = r.B_hist
+        r.B_move = move_from_history(dense, None if B_init is None else _as_dev(B_init, dev))
+        r.extra["move_path"] = "dense"
+        slots = torch.as_tensor(h_epochs, dtype=torch.int64, device=dev)
+        hist_user = (out or {}).get("B_hist")
+        r.B_hist, r.hist_epochs = None, None
+        if want_hist or hist_user is not None:
+            h = dense if len(h_epochs) == E else dense.index_select(0, slots)
+            if h_bf16:
+                h = h.to(torch.bfloat16)
+            if hist_user is not None:
+                if hist_user.dtype != h.dtype or tuple(hist_user.shape) != tuple(h.shape):
+                    raise ValueError(f"out['B_hist'] is {hist_user.dtype} {tuple(hist_user.shape)}, the history asked "
+                                     f"for {h.dtype} {tuple(h.shape)}")
+                h = hist_user.copy_(h)
+            r.B_hist, r.hist_epochs = h, h_epochs
+        if watch_host is not None:
+            r.B_watch = dense.index_select(0, slots).index_select(3, watch_host.to(dev)).contiguous()
+            r.watch_cols = tuple(int(c) for c in watch_host.tolist())
+            r.hist_epochs = h_epochs
+            r.extra["watch_path"], r.extra["watch"] = "dense", None
+        return r
+
+    out_names = tuple(want) + tuple(k for k, v in (out or {}).items() if v is not None and k != "B_hist")
+    if want_move and (want_hist or (out or {}).get("B_hist") is not None
+                      or not move_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs)):
+        return move_dense()
     # a watch list the engine does not take natively rides on an fp32 history of the run's own
     watch_dense = watch_host is not None and (
         single_call or not watch_native(variant, N, E, V, M, watch_host.numel(), shared_inputs=shared_inputs))
@@ -1002,6 +1134,9 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                 raise EngineError("a captured run cannot expand its inputs: sched= needs "
                                   "sched_native(variant, N, E, K, V, M, ...) and vector-aligned buffers")
             W, S = _take_slices(W, sched_host.to(dev)), _take_slices(S, sched_host.to(dev))
+    if want_move and not _vector_form(W, w_u16, B_init, Wprev_init, o, False):  # (nothing is launched yet)
+        return move_dense()
+    b_move = torch.empty((E, N, 2), dtype=torch.float32, device=dev) if want_move else None  # (the engine zeroes it)
     watch_arg = None
     if watch_host is not None and not watch_dense:
         if (isinstance(watch, torch.Tensor) and watch.device == dev and watch.dtype == torch.int32
@@ -1034,7 +1169,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         _launch(lib, dev, (variant, prm.data_ptr(), N, E), K, sched_dev,
                 (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
                  workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
-                capture=capture, phase_ms=phase_ms, watch=watch_arg)
+                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -1043,11 +1178,14 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     if sched is not None:  # how the schedule was taken: by the engine, or expanded to a slice per epoch
         keep["sched_path"] = "native" if sched_dev is not None else "expanded"
         keep["sched"] = sched_dev
+    if want_move:
+        keep["move_path"] = "native"
     hist = o.get("B_hist")
     if h_bf16 and hist is not None and not hist_native:  # the fp32 history, rounded to nearest even
         hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)
     if watch_host is None:
-        return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs)
+        return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs,
+                         B_move=b_move)
     keep["watch_path"] = "dense" if watch_dense else "native"
     if watch_dense:  # the columns of the run's fp32 history (o: before any bfloat16 conversion)
         b_watch = o["B_hist"].index_select(3, watch_host.to(dev)).contiguous()
@@ -1057,7 +1195,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     else:
         keep["watch"] = watch_dev
     return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, h_epochs, b_watch,
-                     tuple(int(c) for c in watch_host.tolist()))
+                     tuple(int(c) for c in watch_host.tolist()), B_move=b_move)
 
 
 class RunGraph:

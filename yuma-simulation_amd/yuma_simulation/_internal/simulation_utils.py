@@ -93,7 +93,7 @@ def _reward_key(config: YumaConfig) -> tuple:
 
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                     want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None,
-                    dedup_inputs: bool = False, bonds_columns=None):
+                    dedup_inputs: bool = False, bonds_columns=None, bonds_movement: bool = False):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
@@ -117,7 +117,18 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     `[:, bonds_columns]` bit for bit -- the servers a chart plots. The engine
     then keeps no [V, M] history (engine.run's watch). Combines with
     bonds_every, dedup_inputs and bonds_dtype (bfloat16: the small fp32
-    watched history, converted)."""
+    watched history, converted).
+    bonds_movement: each run's tuple gains a fourth element, a [E, 2] CPU fp32
+    tensor: per epoch the largest |B_t - B_{t-1}| and the largest |B_t| over
+    the run's bond matrix (engine.run's want_move; engine.settled_epoch reads
+    it: when did the bonds stop moving). Every epoch is covered whatever
+    bonds_every says. With want_bonds=False -- the intended use -- Yuma 3 /
+    Yuma 4 runs whose miner count is a multiple of 4 (engine.move_native; the
+    built-in two-server cases are not) keep no bond history at all; otherwise,
+    and for the other versions, it is reduced from the run's history on the
+    device. The first
+    three elements keep the default call's bits. Combines with bonds_every,
+    bonds_dtype, dedup_inputs and bonds_columns."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
     if bonds_dtype not in (None, torch.float32, torch.bfloat16):
@@ -136,7 +147,7 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     with _no_cyclic_gc():
         return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every),
                                 bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs),
-                                bonds_columns=bonds_columns)
+                                bonds_columns=bonds_columns, bonds_movement=bool(bonds_movement))
 
 
 @contextmanager
@@ -194,7 +205,7 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
                      totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False,
-                     bonds_columns=None):
+                     bonds_columns=None, bonds_movement: bool = False):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -240,7 +251,8 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
         watch = bonds_columns if want_bonds else None  # the watched columns in place of the [V, M] history
         launched.append((E, V, idx, S_host, engine.run(
             variant, params, W, S, want_hist=want_bonds and watch is None, hist_stride=bonds_every, sched=sched,
-            hist_dtype=bonds_dtype if want_bonds and watch is None else None, watch=watch)))
+            hist_dtype=bonds_dtype if want_bonds and watch is None else None, watch=watch,
+            **({"want_move": True} if bonds_movement else {}))))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
         hist = None
@@ -249,6 +261,7 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
         elif want_bonds:
             hist = res.B_hist.cpu()
         inc = res.I.cpu() if want_incentives else None
+        move = res.B_move.cpu() if bonds_movement else None
         # the dividend ratio of the whole group in one pass of the same
         # elementwise ops when its runs share the reward scalars (the sheet)
         ratio = None
@@ -278,7 +291,7 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
                 div = _dividends_per_1000_tao(r.case, r.yuma_config, packed[k][3].cpu(), Dn[:, j])
             bonds = [hist[e, j].clone().to(home) for e in range(hist.shape[0])] if want_bonds else []
             incentives = [inc[e, j].clone().to(home) for e in range(E)] if want_incentives else []
-            results[k] = (div, bonds, incentives)
+            results[k] = (div, bonds, incentives, move[:, j].clone()) if bonds_movement else (div, bonds, incentives)
     return results
 
 
