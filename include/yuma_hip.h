@@ -417,6 +417,79 @@ int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, in
 int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
 
 /* ------------------------------------------------------------------------
+ * Bond reset events: any number of column resets inside one run.
+ *
+ * A subnet deregisters miners all the time, and every deregistration clears
+ * that UID's bonds; yuma_params_t carries one reset per scenario and run.
+ * yuma_run_resets takes a list events_dev [n_events] of yuma_reset_event_t in
+ * DEVICE memory. An event (epoch t, scenario n, column c, mode) applies
+ * B[n][:, c] = 0 before epoch t's update of scenario n, if a bond state exists
+ * and the mode's rule holds:
+ *  - a bond state exists when t >= 1, or t == 0 and B_init is given;
+ *  - YUMA_RESET_ALWAYS always fires;
+ *  - YUMA_RESET_IF_ZERO_CONSENSUS fires iff t >= 1 and C[t-1][n][c] == 0.0f,
+ *    C the quantised server_consensus_weight (at t == 0 it never fires, as
+ *    the scenario's own conditional reset);
+ *  - c == -1 means every column, for YUMA_RESET_ALWAYS only; with the
+ *    conditional mode such an event is ignored;
+ *  - duplicates are allowed and the order does not matter;
+ *  - an event whose epoch is outside [0, E), scenario outside [0, N), column
+ *    outside [-1, M) or mode any other value is ignored by the device code
+ *    and never causes an access outside a buffer (the host cannot check a list
+ *    in device memory without a synchronisation);
+ *  - the scenario's own reset in yuma_params_t keeps working beside the events.
+ * The history holds the state after the update, so a reset at t shows in slot
+ * t. Every output has the bits of the chain of yuma_run_opts calls cut at the
+ * event epochs, each resumed from the previous B_final with the columns
+ * zeroed; the result does not depend on chunk_epochs (an event at a chunk's
+ * first epoch reads C of the previous chunk's last epoch).
+ *
+ * The arguments are yuma_run_opts's with events_dev and n_events after `out`.
+ * n_events == 0 with a NULL list is exactly yuma_run_opts: the same launches
+ * and the yuma_workspace_bytes size. Otherwise the workspace is
+ * yuma_workspace_bytes_resets (>= yuma_workspace_bytes): the difference is a
+ * table of one bit per (epoch, scenario, column), bytes [E][N][ceil(M / 8)],
+ * which the engine zeroes with a small kernel and a resolve kernel (one thread
+ * per event, after the phase that leaves C) fills with atomic ORs; the bond
+ * scan loads a lane's nibble of it beside its other per-epoch inputs and
+ * clears the state with an AND mask, branch-free. A graph re-reads the list at every replay:
+ * rewrite it in place between replays like any other input.
+ *
+ * Native (yuma_resets_native returns 1; host only, makes no HIP call; of `out`
+ * it reads only which pointers are non-NULL; `flags` are the run's flags):
+ * Yuma 3 and Yuma 4 (scalar or liquid alpha, any params reset), the vector
+ * form (M % 4 == 0, with the alignments YUMA_RUN_W_U16 states), fp32 weights,
+ * any V up to YUMA_MAX_VALIDATORS, no YUMA_RUN_SHARED_INPUTS, no
+ * YUMA_RUN_W_U16, no YUMA_RUN_HIST_BF16, none of Wn / Wc / Wb / B_inst / Tv
+ * requested; the fp32 history dense, strided or absent -- the calls whose scan
+ * is YUMA_ELEM_WIDE, YUMA_ELEM_TILE_HIST, YUMA_ELEM_FLAT1 or YUMA_ELEM_FLAT2.
+ * Elsewhere the entry points return YUMA_EUNSUPPORTED before the first launch
+ * and the caller cuts the run at the event epochs itself. Schedules, watch
+ * lists and B_move are not taken by these entry points.
+ *
+ * Refusals, in this order, all before the first launch and without a HIP call
+ * (yuma_graph_create_resets: the same code and yuma_last_error text, before
+ * the capture opens): the options (as yuma_run_opts); [the graph handle];
+ * sizes; NULL params / W / S / out / workspace; n_events < 0, then
+ * n_events > 0 with a NULL list (YUMA_EINVAL); the workspace size
+ * (YUMA_EWORKSPACE); the events not native, then not in vector form
+ * (YUMA_EUNSUPPORTED).
+ * ---------------------------------------------------------------------- */
+typedef struct yuma_reset_event {
+  int32_t epoch;    /* the reset precedes this epoch's update                  */
+  int32_t scenario; /* 0 <= scenario < N                                       */
+  int32_t column;   /* miner column, or -1: every column (YUMA_RESET_ALWAYS)   */
+  int32_t mode;     /* YUMA_RESET_ALWAYS or YUMA_RESET_IF_ZERO_CONSENSUS       */
+} yuma_reset_event_t; /* 16 bytes */
+size_t yuma_workspace_bytes_resets(int variant, int N, int E, int V, int M, int full_outputs);
+int yuma_run_resets(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
+                    const float* W, const float* S, const float* B_init, const float* Wprev_init,
+                    const yuma_outputs_t* out, const yuma_reset_event_t* events_dev, int n_events,
+                    void* workspace, size_t workspace_bytes, int chunk_epochs,
+                    const yuma_run_options_t* opts, void* stream, float* phase_ms);
+int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
+
+/* ------------------------------------------------------------------------
  * Which bond scan a call reaches. Host only, needs no GPU and makes no HIP
  * call: the engine's own choice (the function its runs call before they launch
  * the scan), reported for the first chunk of yuma_run_opts / yuma_run_sched
@@ -525,6 +598,12 @@ int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t
                            const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
                            float* B_watch, float* B_move, void* workspace, size_t workspace_bytes,
                            int chunk_epochs, const yuma_run_options_t* opts);
+/* yuma_graph_create_opts with reset events (yuma_run_resets's arguments). */
+int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                             int E, int V, int M, const float* W, const float* S,
+                             const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                             const yuma_reset_event_t* events_dev, int n_events, void* workspace,
+                             size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts);
 /* Replay on `stream` (stream-ordered, no host synchronisation). */
 int yuma_graph_launch(yuma_graph_t graph, void* stream);
 /* Kernel nodes in the captured graph (diagnostics / tests). */

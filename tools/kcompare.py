@@ -55,6 +55,12 @@ def kernels(lib, every=False):
 
 
 def key(name):
+    # <..., SC, MV, RL = false> takes ElemArgs<SC, MV, RL>: the name of before the reset events (RL = true,
+    # BondArgsRl: only in a library that has them)
+    name = re.sub(r"Lb0EEEvNSt11conditionalIXT8_ENS_10BondArgsRlENS3_IXT7_ENS3_IXT6_ENS_12BondArgsScMvENS_10BondArgsMvEE"
+                  r"4typeENS3_IXT6_ENS_10BondArgsScENS_8BondArgsEE4typeEE4typeEE4typeE$",
+                  "EEvNSt11conditionalIXT7_ENS3_IXT6_ENS_12BondArgsScMvENS_10BondArgsMvEE4typeENS3_IXT6_"
+                  "ENS_10BondArgsScENS_8BondArgsEE4typeEE4typeE", name)
     # <..., SC, MV = false> takes ElemArgs<SC, MV>: the name of before the bond movement (MV = true, BondArgsMv /
     # BondArgsScMv: only in a library that has it)
     name = re.sub(r"Lb0EEEvNSt11conditionalIXT7_ENS3_IXT6_ENS_12BondArgsScMvENS_10BondArgsMvEE4typeENS3_IXT6_"

@@ -1,0 +1,109 @@
+"""The vector-memory waits of k_bonds_elem's RL (reset event) forms beside their
+plain twins, from the library's gfx950 code object (no GPU needed): for each
+pair the s_waitcnt vmcnt(N) instructions inside the epoch loop (the largest
+backward-branch range of the kernel and the out-of-line blocks that branch
+back into it) and outside it, the byte loads of the
+reset table, and the register report (VGPRs, SGPRs, spills, scratch).
+    python tools/kwaits.py [libyuma_hip.so] > profiles/resets/waitcnt.txt
+A prefetch ring that is intact shows counted waits (vmcnt(N), N > 0) in the
+loop; a vmcnt(0) in the loop that the twin lacks is a drain."""
+import collections
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kcompare  # noqa: E402
+
+RL_TAIL = "Lb1EEEvNSt11conditionalIXT8"
+
+
+def disassemble(lib):
+    """mangled name -> [(offset in the function, instruction text)]"""
+    with tempfile.TemporaryDirectory() as t:
+        subprocess.run([f"{kcompare.LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={t}/fb", lib], check=True)
+        subprocess.run([f"{kcompare.LLVM}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={t}/fb",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={t}/co"], check=True)
+        text = subprocess.run([f"{kcompare.LLVM}/llvm-objdump", "-d", f"{t}/co"], capture_output=True, text=True,
+                              check=True).stdout
+    out, cur, start = {}, None, 0
+    for line in text.splitlines():
+        m = re.match(r"^([0-9a-f]+) <(\S+)>:", line)
+        if m:
+            start, cur = int(m.group(1), 16), m.group(2)
+            out[cur] = []
+            continue
+        m = re.match(r"^\s+\S.*?// ([0-9A-F]+):", line)
+        if m and cur is not None:
+            out[cur].append((int(m.group(1), 16) - start, line.strip()))
+    return out
+
+
+def target(text, name):
+    m = re.search(r"<" + re.escape(name) + r"\+0x([0-9a-f]+)>", text) if "s_cbranch" in text or "s_branch" in text else None
+    return int(m.group(1), 16) if m else None
+
+
+def loop_ranges(ins, name):
+    """The epoch loop as offset ranges: the largest backward-branch range, and
+    the out-of-line blocks behind it that the loop branches to and that branch
+    back into it (the compiler parks rare blocks and, in the HS kernels, the
+    refill blocks there)."""
+    best = (0, -1)
+    for off, text in ins:
+        t = target(text, name)
+        if t is not None and "s_cbranch" in text and t <= off and off - t > best[1] - best[0]:
+            best = (t, off)
+    ranges = [best]
+    inside = lambda o: any(lo <= o <= hi for lo, hi in ranges)
+    offs = [o for o, _ in ins]
+    changed = best[1] >= 0
+    while changed:
+        changed = False
+        starts = sorted({t for o, x in ins if inside(o) for t in [target(x, name)] if t is not None and not inside(t)})
+        for s in starts:
+            if s not in offs:
+                continue
+            for o, x in ins[offs.index(s):]:
+                if "s_endpgm" in x:
+                    break
+                t = target(x, name)
+                if t is not None and "s_branch" in x and not inside(o):
+                    if inside(t):
+                        ranges.append((s, o))
+                        changed = True
+                    break
+    return ranges
+
+
+def waits(ins, name):
+    ranges = loop_ranges(ins, name)
+    inside, outside, loads = collections.Counter(), collections.Counter(), 0
+    for off, text in ins:
+        m = re.search(r"s_waitcnt.*?vmcnt\((\d+)\)", text)
+        if m:
+            (inside if any(lo <= off <= hi for lo, hi in ranges) else outside)[f"vmcnt({m.group(1)})"] += 1
+        loads += "global_load_ubyte" in text
+    fmt = lambda c: " ".join(f"{k} x{v}" for k, v in sorted(c.items(), key=lambda kv: int(kv[0][6:-1]))) or "-"
+    return f"loop [{fmt(inside)}]  outside [{fmt(outside)}]  byte loads {loads}"
+
+
+def main():
+    lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(kcompare.ROOT, "yuma-simulation_amd", "lib", "libyuma_hip.so")
+    code, meta = disassemble(lib), kcompare.kernels(lib)
+    print("k_bonds_elem RL forms and their plain twins: s_waitcnt vmcnt(N) in the epoch loop and outside it;")
+    print("registers: " + " ".join(kcompare.FIELDS))
+    for name in sorted(code):
+        if "k_bonds_elem" not in name or RL_TAIL not in name:
+            continue
+        twin = name.replace(RL_TAIL, RL_TAIL.replace("Lb1", "Lb0", 1))
+        s = re.search(r"k_bonds_elemILi(\d)ENS_9ElemShapeI(.*?)EEE(.*?)EEvN", name)
+        print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
+        for tag, k in (("RL   ", name), ("plain", twin)):
+            print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
+
+
+if __name__ == "__main__":
+    main()

@@ -3279,9 +3279,14 @@ struct BondArgsMv : BondArgs {
 struct BondArgsScMv : BondArgsSc {
   float* B_move;
 };
-template <bool SC, bool MV>
-using ElemArgs = std::conditional_t<MV, std::conditional_t<SC, BondArgsScMv, BondArgsMv>,
-                                    std::conditional_t<SC, BondArgsSc, BondArgs>>;
+// ... with reset events (k_bonds_elem<.., RL = true>): the resolved table
+struct BondArgsRl : BondArgs {
+  const unsigned char* rmask;  // [E][N][ceil(M / 8)]: bit c & 7 of byte c >> 3 set = column c is zeroed (k_reset_events)
+};
+template <bool SC, bool MV, bool RL = false>
+using ElemArgs = std::conditional_t<RL, BondArgsRl,
+                                    std::conditional_t<MV, std::conditional_t<SC, BondArgsScMv, BondArgsMv>,
+                                                       std::conditional_t<SC, BondArgsSc, BondArgs>>>;
 __host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
   return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
 }
@@ -4112,6 +4117,20 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // independent, so the result is bit-defined. The MV instantiations take
 // BondArgsMv / BondArgsScMv, the records with the pointer appended; every
 // other instantiation keeps its argument block and its code.
+// RL: reset events (yuma_run_resets). k_reset_events has resolved every event
+// of the chunk into the table rmask, one bit per (epoch, scenario, column),
+// bytes [E][N][ceil(M / 8)]: both of an event's conditions (a bond state
+// exists; C of the previous epoch is zero) are functions of the inputs alone.
+// A lane's four columns are one nibble of one byte: the byte joins the
+// register ring in fetch() as one more unconditional load per epoch in flight,
+// (first: loads return in order, and it is the first value an epoch reads),
+// and at the top of the epoch every row of the lane is cleared branch-free
+// (B = bit ? 0 : B, as an AND mask), never a load in the loop's rare path
+// (which would drain the ring, see zero_c below). The RL instantiations take
+// BondArgsRl, the record with the table pointer appended; every other
+// instantiation keeps its argument block and its code. Yuma 3 / Yuma 4 in
+// vector form with fp32 weights and an fp32 history or none, no schedule and
+// no movement: the four shapes plan_scan picks there.
 // SH: the block shape, an ElemShape (R, P, BS, CB as above; VECI: float4
 // incentive / bond_alpha loads; NT: non-temporal history stores; DPL: the
 // dividend-partial layout).
@@ -4121,13 +4140,16 @@ struct ElemShape {
   static constexpr bool VECI = VECI_, NT = NT_;
 };
 template <int VARIANT, typename SH, bool VEC, bool RQ = false, typename WT = float, bool HS = false,
-          typename HT = float, bool SC = false, bool MV = false>
-__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV> A) {
+          typename HT = float, bool SC = false, bool MV = false, bool RL = false>
+__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RL> A) {
   constexpr int R = SH::R, P = SH::P, BS = SH::BS, CB = SH::CB, DPL = SH::DPL;
   constexpr bool VECI = SH::VECI, NT = SH::NT;
   static_assert(!MV || (VEC && DPL == DP_QTE && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<HT, float> && !HS),
                 "bond movement: Yuma 3 / Yuma 4, vector form, the history-less flat shapes");
   static_assert(!SC || (VEC && VARIANT >= YUMA_VARIANT_YUMA3), "input schedules: Yuma 3 / Yuma 4, vector form");
+  static_assert(!RL || (VEC && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float> && std::is_same_v<HT, float> &&
+                        !SC && !MV),
+                "reset events: Yuma 3 / Yuma 4, vector form, fp32 weights and history, no schedule, no movement");
   static_assert(std::is_same_v<HT, float> || (std::is_same_v<HT, __bf16> && NT && VEC && !RQ &&
                                               VARIANT >= YUMA_VARIANT_YUMA3),
                 "bf16 history: Yuma 3 / Yuma 4, vector form, non-temporal stores");
@@ -4218,6 +4240,22 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV> A) {
   float rd[P][R], rsn[P][R], ri[P][4], rba[P][4];
   float rcc[COLNORM ? P : 1][4], rcs[COLNORM ? P : 1][4], rcr[COLNORM ? P : 1][4];  // Yuma / Yuma2: C, csb, csr
   float rrq[RQ ? P : 1][RQ ? R : 1];  // RQ: k_rowsum's screened RN(1 / row sum) (rq4.y)
+  // RL: the byte of the reset table that holds this lane's nibble (M % 4 == 0:
+  // m & 4 selects it); lanes at m >= M read the row's last byte, their columns
+  // never reach an output. The lane walks the table with a pointer of its own
+  // (rnext, stepped by one epoch's N rows at every fetch: fetches come in
+  // epoch order), held in vector registers with its step: the address as
+  // slice * row bytes + lane byte cost the history shapes scalar registers
+  // they do not have (2-12 spilled into lanes inside the epoch loop)
+  [[maybe_unused]] unsigned rmk[RL ? P : 1];
+  [[maybe_unused]] const unsigned char* rnext = nullptr;
+  [[maybe_unused]] int rstep = 0;
+  if constexpr (RL) {
+    const int rmb = (M + 7) >> 3;
+    rnext = A.rmask + ((long long)A.t0 * N + n) * rmb + min(m >> 3, rmb - 1);
+    rstep = N * rmb;
+    asm("" : "+v"(rstep));  // (an empty statement: it only names the register class)
+  }
   // DP_QTE: the quad partials of up to kQBuf epochs parked in LDS (one float
   // per wave row and epoch) and written out as contiguous runs when the
   // buffer fills or the launch ends: no global store inside the epoch loop
@@ -4246,6 +4284,15 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV> A) {
   auto fetch = [&](int k, int t, int sk) {
     const long long slice = (long long)t * N + n;
     const long long cslice = (long long)t * N + ncs;
+    // RL: the table byte first. It is the first value the epoch reads, and
+    // memory loads return in order: a wait for it leaves the rest of this
+    // fetch in flight. (Issued last, wherever the register allocator made it
+    // the unused odd half of a packed-FMA operand pair, the waitcnt pass put
+    // a vmcnt(0) in front of that FMA: a ring drain in every epoch.)
+    if constexpr (RL) {
+      rmk[k] = *rnext;
+      rnext += rstep;
+    }
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const int rr = min(row0 + G * i, V - 1);
@@ -4321,6 +4368,23 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV> A) {
               for (int cc = 0; cc < 4; ++cc)
                 if (reset_all || cc == c) B[i][cc] = 0.0f;
           }
+        }
+      }
+      if constexpr (RL) {
+        // The events of this epoch, resolved (a state that does not exist is
+        // all zeros already): one AND mask per column of the lane's nibble, in
+        // a vector register -- all ones, or 0 where the bit is set; x & 0 is
+        // +0.0f, the value a reset stores. The empty asm statement only pins
+        // the mask to a vector register: left alone, the optimiser rewrites
+        // the AND as compare-and-select, whose four lane masks live in scalar
+        // registers, which the history shapes do not have.
+        const unsigned nib = rmk[k] >> (m & 4);
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+          unsigned keep = ((nib >> cc) & 1u) - 1u;
+          asm("" : "+v"(keep));
+#pragma unroll
+          for (int i = 0; i < R; ++i) B[i][cc] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, B[i][cc]) & keep);
         }
       }
       float bac[4], omba[4];
@@ -4584,6 +4648,51 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV> A) {
 // from zero.
 __global__ __launch_bounds__(256) void k_move_zero(float* p, long long n) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) p[i] = 0.0f;
+}
+
+// Reset events (yuma_run_resets): the events of the epochs [t0, t1) resolved
+// into the table rmask (bytes [E][N][ceil(M / 8)], addressed as 32-bit words:
+// the engine pads it to whole words and has zeroed it with k_move_zero before
+// the run's first chunk), one thread per event, after the phase that left C
+// for the chunk (C of epoch t0 - 1 is the previous chunk's). An event fires
+// if a bond state exists (t >= 1, or B_init given: has_init) and its mode's
+// rule holds: ALWAYS; IF_ZERO_CONSENSUS iff t >= 1 and C[t-1][n][c] == 0
+// (never for column -1). Column -1 (ALWAYS) sets the scenario's whole row.
+// Every field is range-checked before it addresses anything: a bad event is
+// ignored. Bits are set with vector integer atomic ORs, so duplicates and any
+// order give the same table.
+__global__ __launch_bounds__(256) void k_reset_events(const yuma_reset_event_t* __restrict__ ev, int n_ev,
+                                                      const float* __restrict__ C, unsigned* __restrict__ rmask,
+                                                      int N, int E, int M, int t0, int t1, int has_init) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_ev) return;
+  const yuma_reset_event_t e = ev[i];
+  const int t = e.epoch, n = e.scenario, c = e.column;
+  if (t < 0 || t >= E || t < t0 || t >= t1 || n < 0 || n >= N || c < -1 || c >= M) return;
+  if (t == 0 && !has_init) return;
+  if (e.mode == YUMA_RESET_IF_ZERO_CONSENSUS) {
+    if (c < 0 || t < 1) return;
+    if (!(C[((long long)(t - 1) * N + n) * M + c] == 0.0f)) return;
+  } else if (e.mode != YUMA_RESET_ALWAYS) {
+    return;
+  }
+  const int mb = (M + 7) >> 3;
+  const long long row = ((long long)t * N + n) * mb;
+  auto or_byte = [&](long long off, unsigned v) { atomicOr(rmask + (off >> 2), v << ((off & 3) * 8)); };
+  if (c >= 0) {
+    or_byte(row + (c >> 3), 1u << (c & 7));
+  } else {
+    // the row's bytes [row, row + mb), a word at a time (the last byte holds M & 7 columns, or 8)
+    const unsigned last = (M & 7) != 0 ? (1u << (M & 7)) - 1u : 0xffu;
+    for (long long w = row >> 2; w <= (row + mb - 1) >> 2; ++w) {
+      unsigned v = 0u;
+      for (int b = 0; b < 4; ++b) {
+        const long long off = w * 4 + b;
+        if (off >= row && off < row + mb) v |= (off == row + mb - 1 ? last : 0xffu) << (b * 8);
+      }
+      atomicOr(rmask + w, v);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -5925,11 +6034,14 @@ struct ScanKey {
   bool csb;      // the rank pass formed the bond column sums (forms_csb)
   bool full;     // W_b or the instantaneous bonds requested
   bool mv;       // the per-epoch bond movement (yuma_run_move; move_native holds)
+  bool rl;       // reset events (yuma_run_resets; resets_native holds)
 };
 // yuma_scan_plan_t as yuma_scan_plan reports it, and the movement choice
 // (the MV instantiation of the flat shape) beside it
+// and the reset-event choice (the RL instantiation of the shape)
 struct ScanPlan : yuma_scan_plan_t {
   int mv;
+  int rl;
 };
 
 // The scan of a chunk: its kernel, that kernel's flags, the grid, and the
@@ -5962,6 +6074,7 @@ ScanPlan plan_scan(const ScanKey& k) {
   p.ptiles = tiles;
   p.dpl = yk::DP_TV;
   p.mv = k.mv;  // (move_native: the key reaches the flat shapes below; launch_scan refuses any other)
+  p.rl = k.rl;  // (resets_native: the key reaches the wide, tile-history and flat shapes; as above)
   // a kernel of `block` threads whose blocks own brows rows x bcols miners of `per` scenarios
   auto plan = [&](int form, int rows, int block, int brows, int bcols, bool rq, int per = 1) {
     p.form = form;
@@ -6027,7 +6140,7 @@ ScanPlan plan_scan(const ScanKey& k) {
 // instantiated where launch_scan is defined, and so keep their place in the
 // code object, behind the kernels of phase 1.)
 void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K,
-                 float* B_move = nullptr);
+                 float* B_move = nullptr, const unsigned char* rmask = nullptr);
 
 // The watched columns' scan over the chunk of A (k_bonds_watch), from the main
 // scan's own arguments: the same inputs, state and history countdown. Enqueued
@@ -6156,6 +6269,28 @@ bool move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* 
   if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, out, flags)) return false;
   return true;
 }
+
+// Whether a run with these arguments applies reset events inside its scan
+// (yuma_resets_native): the element-wise variants in vector form, fp32 weights,
+// any validator count, per-scenario inputs, an fp32 history (dense or strided)
+// or none, none of the per-epoch matrices requested -- exactly the calls
+// plan_scan sends to the wide, tile-history and flat shapes. Only those are
+// instantiated with RL.
+bool resets_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || V < 1 || M < 1 || V > YUMA_MAX_VALIDATORS || (M % 4) != 0) return false;
+  if (flags & (YUMA_RUN_SHARED_INPUTS | YUMA_RUN_W_U16 | YUMA_RUN_HIST_BF16)) return false;
+  if (out != nullptr && (out->Wn || out->Wc || out->Wb || out->B_inst || out->Tv)) return false;
+  return true;
+}
+
+// Bytes of the reset table of a run (bytes [E][N][ceil(M / 8)], padded to the
+// 256-byte granule the workspace is carved in; k_reset_events addresses it as
+// 32-bit words) and its offset behind the carved workspace of ws_bytes bytes
+size_t reset_table_bytes(int N, int E, int M) {
+  return ((size_t)E * (size_t)N * (size_t)((M + 7) >> 3) + 255) & ~(size_t)255;
+}
+size_t reset_table_offset(size_t ws_bytes) { return (ws_bytes + 255) & ~(size_t)255; }
 
 // What run_plan and shard_stage_impl decide alike.
 int check_sizes(int variant, int N, int E, int V, int M) {
@@ -6288,6 +6423,11 @@ struct RunReq {
   // (n_watch = 0 with NULL watch / B_watch: has_watch stays 0)
   int has_move = 0;
   float* B_move = nullptr;
+  // yuma_run_resets (has_resets): the events events[n_events] (device memory); n_events = 0 with a NULL list
+  // leaves has_resets 0, the run yuma_run_opts makes
+  int has_resets = 0;
+  const yuma_reset_event_t* events = nullptr;
+  int n_events = 0;
 };
 
 // The history countdown (BondArgs::hnext) of the chunk from epoch A.t0 of the
@@ -6323,6 +6463,7 @@ ScanKey scan_key(const RunReq& q, bool vec, bool sched, bool run, bool strided) 
   k.csb = forms_csb(q.variant, q.V, q.out);
   k.full = q.out->Wb != nullptr || q.out->B_inst != nullptr;
   k.mv = q.has_move != 0;
+  k.rl = q.has_resets != 0;
   return k;
 }
 
@@ -6330,6 +6471,7 @@ ScanKey scan_key(const RunReq& q, bool vec, bool sched, bool run, bool strided) 
 // set of an input schedule's K stored slices), the vector form, the shapes.
 struct RunPlan {
   Workspace ws, wk;
+  size_t rmask_off;  // reset events: the table's offset in the workspace
   bool vec;
   int tiles;
   RowCfg rc;
@@ -6352,6 +6494,18 @@ int check_native(const RunReq& q, bool vec, bool sched, int K) {
     if (!vec)
       return fail(YUMA_EUNSUPPORTED,
                   "an input schedule (yuma_sched_native) needs the vector form: W vector-aligned and the fp32 "
+                  "matrices 16-byte aligned");
+  }
+  if (q.has_resets) {
+    const int f = (wsh ? YUMA_RUN_SHARED_INPUTS : 0) | (q.w_u16 ? YUMA_RUN_W_U16 : 0) | (q.hist_bf16 ? YUMA_RUN_HIST_BF16 : 0);
+    if (!resets_native(variant, N, E, V, M, out, f))
+      return fail(YUMA_EUNSUPPORTED,
+                  "reset events are not native for variant=%d V=%d M=%d flags=0x%x or the requested outputs "
+                  "(yuma_resets_native): cut the run at the event epochs",
+                  variant, V, M, f);
+    if (!vec)
+      return fail(YUMA_EUNSUPPORTED,
+                  "reset events (yuma_resets_native) need the vector form: W vector-aligned and the fp32 "
                   "matrices 16-byte aligned");
   }
   if (q.has_watch && !watch_native(variant, N, E, V, M, q.n_watch, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
@@ -6433,14 +6587,18 @@ int run_plan(const RunReq& q, RunPlan* p) {
       return fail(YUMA_EINVAL, "n_watch=%d: N V n_watch elements exceed the watch kernel's grid", q.n_watch);
   }
   if (q.has_move && q.B_move == nullptr) return fail(YUMA_EINVAL, "B_move is NULL");
+  if (q.n_events < 0) return fail(YUMA_EINVAL, "n_events=%d must not be negative", q.n_events);
+  if (q.n_events > 0 && q.events == nullptr) return fail(YUMA_EINVAL, "n_events=%d with a NULL event list", q.n_events);
   const int full = out->Tv != nullptr;
   // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
   // params live in device memory, so the Python marshaller enforces it.
   p->ws = carve((char*)q.workspace, variant, N, E, V, M, full);
   p->wk = q.sched ? carve((char*)q.workspace + p->ws.bytes, variant, N, K, V, M, 0, true) : Workspace{};
-  if (p->ws.bytes + p->wk.bytes > q.ws_bytes)
-    return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)",
-                q.ws_bytes, p->ws.bytes + p->wk.bytes, full);
+  // (reset events: the table behind the carved workspace; they come without a schedule)
+  p->rmask_off = q.has_resets ? reset_table_offset(p->ws.bytes) : 0;
+  const size_t need = q.has_resets ? p->rmask_off + reset_table_bytes(N, E, M) : p->ws.bytes + p->wk.bytes;
+  if (need > q.ws_bytes)
+    return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)", q.ws_bytes, need, full);
   p->tiles = (M + yk::kTileM - 1) / yk::kTileM;
   p->rc = row_cfg(V);
   const bool vec = p->vec = vector_form(M, q.W, q.B_init, q.Wprev_init, out, q.hist_bf16 != 0, q.w_u16 ? 2 : 4);
@@ -6606,11 +6764,23 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     const long long nm = (long long)E * N * 2;
     YK_LAUNCH(yk::k_move_zero, (nm + 255) / 256 < 1024 ? (nm + 255) / 256 : 1024, 256, st, q.B_move, nm);
   }
+  // reset events: the table zeroed before the first chunk (k_move_zero: all-zero
+  // bits, a kernel node for the reason given there), then each chunk's events
+  // resolved once phase 1 has left the chunk's C
+  unsigned char* const rmask = q.has_resets ? (unsigned char*)q.workspace + plan.rmask_off : nullptr;
+  if (q.has_resets) {
+    const long long nw = (long long)(reset_table_bytes(N, E, M) / 4);
+    YK_LAUNCH(yk::k_move_zero, (nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024, 256, st,
+              reinterpret_cast<float*>(rmask), nw);
+  }
   for (int c0 = 0; c0 < E; c0 += chunk) {
     const int c1 = c0 + chunk < E ? c0 + chunk : E;
     const long long s0 = (long long)c0 * N;
     const long long ns = (long long)(c1 - c0) * N;
     if (sched == nullptr) phase1(ws, buf, c0, c1);
+    if (q.has_resets && q.n_events > 0)  // (counted under YUMA_PHASE_INCENTIVE, the phase it follows)
+      YK_LAUNCH(yk::k_reset_events, ((long long)q.n_events + 255) / 256, 256, st, q.events, q.n_events, buf.C,
+                reinterpret_cast<unsigned*>(rmask), N, E, M, c0, c1, B_init != nullptr ? 1 : 0);
 
     // (A.W: the scan is launched for WT)
     yk::BondArgs A = bond_args(reinterpret_cast<const float*>(W), ws, buf, prm, B_init, Wprev_init, out, csb, N,
@@ -6626,7 +6796,7 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     if (q.has_watch)  // (Yuma 3 / Yuma 4: run_plan) the state before epoch c0 is still in A.Bstate
       launch_watch<WT>(st, variant, A, q.watch, q.n_watch, q.B_watch, sched, K);
     const ScanPlan scan = plan_scan(scan_key(q, vec, sched != nullptr, true, yk::hist_strided(A)));
-    launch_scan(st, scan, A, sched, K, q.B_move);
+    launch_scan(st, scan, A, sched, K, q.B_move, rmask);
     const int ptiles = scan.ptiles;
     int dpl = scan.dpl;
     tm.mark(YUMA_PHASE_FINALIZE);
@@ -6818,10 +6988,43 @@ using Mode = std::integral_constant<int, MODE>;
 // written at each kernel are the instantiated set, in this one place; any
 // other plan aborts (bad_plan).
 template <int VARIANT, bool VEC, typename WT, bool SC>
-void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move) {
+void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move,
+                    const unsigned char* rmask) {
   constexpr bool kPlain = std::is_same_v<WT, float> && !SC;  // fp32 W, no schedule
   constexpr bool kColnorm = VARIANT <= YUMA_VARIANT_YUMA2, kElem34 = VARIANT >= YUMA_VARIANT_YUMA3;
   const long long nb = p.grid;
+  if constexpr (kElem34 && VEC && kPlain) {
+    // reset events (RL; BondArgsRl): the four shapes plan_scan picks for Yuma 3
+    // / Yuma 4 in vector form with fp32 weights, each with the RQ it picks
+    // there (the flat shapes always, the history shapes never), the history
+    // shapes dense or strided, no bfloat16 history, no movement
+    if (p.rl) {
+      auto elem_rl = [&](auto sh, auto RQ, auto hs_mode) {
+        using SH = decltype(sh);
+        constexpr bool kRq = decltype(RQ)::value;
+        if ((p.rq != 0) != kRq || p.hist_bf16 || p.mv) bad_plan(p);
+        with_flag<decltype(hs_mode)::value>(p, p.hs, [&](auto HS) {
+          yk::BondArgsRl As{};
+          static_cast<yk::BondArgs&>(As) = A;
+          As.rmask = rmask;
+          YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, kRq, float, decltype(HS)::value, float, false, false, true>),
+                    nb, SH::BS, st, As);
+        });
+      };
+      if (p.form == YUMA_SCAN_ELEM) switch (p.shape) {
+          case YUMA_ELEM_WIDE:
+            return elem_rl(ElemWide<VARIANT>{}, std::false_type{}, Mode<kEither>{});
+          case YUMA_ELEM_TILE_HIST:
+            return elem_rl(ElemTileHist<true>{}, std::false_type{}, Mode<kEither>{});
+          case YUMA_ELEM_FLAT1:
+            return elem_rl(ElemFlat1<true>{}, std::true_type{}, Mode<kNever>{});
+          case YUMA_ELEM_FLAT2:
+            return elem_rl(ElemFlat2<true>{}, std::true_type{}, Mode<kNever>{});
+        }
+      bad_plan(p);
+    }
+  }
+  if (p.rl) bad_plan(p);
   [[maybe_unused]] auto go = [&](auto kern) { YK_LAUNCH(kern, nb, p.block, st, A); };
   if constexpr (kColnorm && kPlain) {
     if (p.form == YUMA_SCAN_TILE && !p.rq)  // k_bonds, by RowCfg
@@ -6944,22 +7147,25 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
 // Launch the bond scan that plan_scan chose, for A.N scenarios over epochs
 // [A.t0, A.t1): the only place a bond scan is instantiated. uint16 weights
 // and input schedules are Yuma 3 / Yuma 4 in vector form (run_plan).
-void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move) {
+void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move,
+                 const unsigned char* rmask) {
   A.rowblocks = p.rowblocks;
   A.cblocks = p.cblocks;
-  if ((p.rq && A.rq4 == nullptr) || (p.sc && sched == nullptr) || (p.mv != 0) != (B_move != nullptr)) bad_plan(p);
+  if ((p.rq && A.rq4 == nullptr) || (p.sc && sched == nullptr) || (p.mv != 0) != (B_move != nullptr) ||
+      (p.rl != 0) != (rmask != nullptr))
+    bad_plan(p);
   with_variant(p.variant, [&](auto VARIANT) {
     constexpr int kVariant = decltype(VARIANT)::value;
     if constexpr (kVariant >= YUMA_VARIANT_YUMA3) {
       if (p.vector_form && p.w_u16)
         return with_bool(p.sc != 0, [&](auto SC) {
-          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K, B_move);
+          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K, B_move, rmask);
         });
-      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K, B_move);
+      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K, B_move, rmask);
     }
     if (p.w_u16 || p.sc) bad_plan(p);
     with_bool(p.vector_form != 0, [&](auto VEC) {
-      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K, B_move);
+      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K, B_move, rmask);
     });
   });
 }
@@ -7014,6 +7220,14 @@ void read_move(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_
   if (n_watch == 0 && watch_dev == nullptr && B_watch == nullptr) q->has_watch = 0;
   q->has_move = 1;
   q->B_move = B_move;
+}
+
+// yuma_run_resets / yuma_graph_create_resets: the event list as given (run_plan refuses what is wrong with it);
+// n_events = 0 with a NULL list is "no events", the run of yuma_run_opts.
+void read_resets(const yuma_reset_event_t* events_dev, int n_events, RunReq* q) {
+  q->has_resets = (n_events != 0 || events_dev != nullptr) ? 1 : 0;
+  q->events = events_dev;
+  q->n_events = n_events;
 }
 
 // A direct run: validate, then enqueue on the caller's stream, in the weight type the request names.
@@ -7141,6 +7355,27 @@ int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, in
   if (const int err = read_opts(opts, &q)) return err;
   read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, &q);
   return run_direct(q);
+}
+
+size_t yuma_workspace_bytes_resets(int variant, int N, int E, int V, int M, int full_outputs) {
+  if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
+  return reset_table_offset(carve(nullptr, variant, N, E, V, M, full_outputs).bytes) + reset_table_bytes(N, E, M);
+}
+
+int yuma_run_resets(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
+                    const float* W, const float* S, const float* B_init, const float* Wprev_init,
+                    const yuma_outputs_t* out, const yuma_reset_event_t* events_dev, int n_events,
+                    void* workspace, size_t workspace_bytes, int chunk_epochs,
+                    const yuma_run_options_t* opts, void* stream, float* phase_ms) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_resets(events_dev, n_events, &q);
+  return run_direct(q);
+}
+
+int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  return resets_native(variant, N, E, V, M, out, flags) ? 1 : 0;
 }
 
 int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
@@ -7277,6 +7512,18 @@ int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t
            chunk_epochs, nullptr, nullptr};
   if (const int err = read_opts(opts, &q)) return err;
   read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, &q);
+  return graph_create_impl(graph, q);
+}
+
+int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                             int E, int V, int M, const float* W, const float* S,
+                             const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                             const yuma_reset_event_t* events_dev, int n_events, void* workspace,
+                             size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_resets(events_dev, n_events, &q);
   return graph_create_impl(graph, q);
 }
 

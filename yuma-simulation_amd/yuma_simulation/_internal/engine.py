@@ -57,6 +57,10 @@ EXPORTED_SYMBOLS = (
     "yuma_run_move",
     "yuma_move_native",
     "yuma_graph_create_move",
+    "yuma_workspace_bytes_resets",
+    "yuma_run_resets",
+    "yuma_resets_native",
+    "yuma_graph_create_resets",
     "yuma_scan_plan",
     "yuma_epoch",
     "yuma_synth_weights",
@@ -141,6 +145,15 @@ class YumaOutputsC(ctypes.Structure):
 
 SHARD_IO_FIELDS = ("rowsum_part", "rowsum", "csum_part", "csum_part_d", "csum", "csum_d",
                    "levels", "rsum_part", "rsum", "levels_all", "dsum_part", "dsum", "tv_part", "tv")
+
+
+class YumaResetEventC(ctypes.Structure):
+    """yuma_reset_event_t (include/yuma_hip.h): 16 bytes."""
+    _fields_ = [("epoch", ctypes.c_int32), ("scenario", ctypes.c_int32), ("column", ctypes.c_int32),
+                ("mode", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(YumaResetEventC) == 16, ctypes.sizeof(YumaResetEventC)
 
 
 class YumaRunOptionsC(ctypes.Structure):
@@ -244,6 +257,18 @@ def load_library(path: str | None = None):
             lib.yuma_graph_create_move.restype = i32
             lib.yuma_move_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
             lib.yuma_move_native.restype = i32
+        # reset events: yuma_run_opts's arguments, the list and its length after `out`
+        if hasattr(lib, "yuma_run_resets"):  # (A/B libraries of older sources lack them)
+            a = lib.yuma_run_opts.argtypes
+            lib.yuma_run_resets.argtypes = a[:11] + [vp, i32] + a[11:]
+            lib.yuma_run_resets.restype = i32
+            a = lib.yuma_graph_create_opts.argtypes
+            lib.yuma_graph_create_resets.argtypes = a[:12] + [vp, i32] + a[12:]
+            lib.yuma_graph_create_resets.restype = i32
+            lib.yuma_workspace_bytes_resets.argtypes = [i32, i32, i32, i32, i32, i32]
+            lib.yuma_workspace_bytes_resets.restype = sz
+            lib.yuma_resets_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
+            lib.yuma_resets_native.restype = i32
         if hasattr(lib, "yuma_scan_plan"):  # (A/B libraries of older sources lack it)
             lib.yuma_scan_plan.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp]
             lib.yuma_scan_plan.restype = i32
@@ -594,6 +619,120 @@ def move_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = 
     return bool(load_library().yuma_move_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
 
 
+def resets_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False,
+                  want: tuple[str, ...] = (), *, shared_inputs: bool = False, w_u16: bool = False,
+                  hist_bf16: bool = False) -> bool:
+    """Whether `run(..., resets=)` with these arguments applies the events
+    inside its bond scan (yuma_resets_native; needs the library, not a GPU):
+    Yuma 3 / Yuma 4, any V, M % 4 == 0, fp32 weights, no shared inputs, an fp32
+    history or none, none of Wn / Wc / Wb / B_inst / Tv wanted. Otherwise `run`
+    cuts the run at the event epochs and RunGraph refuses."""
+    names = {"Dn", "C", "I", "B_final", *want}
+    if want_hist:
+        names.add("B_hist")
+    outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
+    flags = ((RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+             | (RUN_HIST_BF16 if hist_bf16 else 0))
+    return bool(load_library().yuma_resets_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
+
+
+def _resets_host(resets, N: int, E: int, M: int) -> torch.Tensor:
+    """A host event list as a CPU int64 tensor [n, 4] of (epoch, scenario,
+    column, mode), validated: integers, epoch in [0, E), scenario in [0, N),
+    column in [-1, M) (-1: every column), mode RESET_ALWAYS or
+    RESET_IF_ZERO_CONSENSUS. ValueError otherwise."""
+    t = resets if isinstance(resets, torch.Tensor) else torch.as_tensor(np.asarray(resets))
+    if t.numel() == 0:
+        return torch.zeros((0, 4), dtype=torch.int64)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"resets must hold integers, not {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != 4:
+        raise ValueError(f"resets must be (epoch, scenario, column, mode) events, shape [n, 4], not {tuple(t.shape)}")
+    h = t.detach().to(device="cpu", dtype=torch.int64)
+    for j, (name, lo, hi) in enumerate((("epoch", 0, E), ("scenario", 0, N), ("column", -1, M))):
+        bad = (h[:, j] < lo) | (h[:, j] >= hi)
+        if bool(bad.any()):
+            k = int(bad.nonzero()[0])
+            raise ValueError(f"resets[{k}]: {name} {int(h[k, j])} is outside [{lo}, {hi})")
+    bad = (h[:, 3] != RESET_ALWAYS) & (h[:, 3] != RESET_IF_ZERO_CONSENSUS)
+    if bool(bad.any()):
+        k = int(bad.nonzero()[0])
+        raise ValueError(f"resets[{k}]: mode {int(h[k, 3])} is neither RESET_ALWAYS nor RESET_IF_ZERO_CONSENSUS")
+    return h
+
+
+def _run_segments(variant, params, W, S, B_init, Wprev_init, ev, *, N, E, M, h_epochs, want_hist, want,
+                  chunk_epochs, workspace, out, shared_inputs, hist_stride) -> "RunResult":
+    """run(..., resets=) where the events are not native: the chain that defines
+    them. The run is cut at the distinct event epochs; each segment runs on the
+    existing path from the carried B_final, whose columns torch zeroes between
+    segments (conditional events read the previous segment's last C); the
+    params' own reset is folded into the event list and cleared in copied
+    records; the history's phase is carried from segment to segment; per-epoch
+    outputs and history slots are concatenated. ev: CPU int64 [n, 4]; events
+    the device code would ignore are dropped here."""
+    dev = device()
+    ok = ((ev[:, 0] >= 0) & (ev[:, 0] < E) & (ev[:, 1] >= 0) & (ev[:, 1] < N) & (ev[:, 2] >= -1) & (ev[:, 2] < M)
+          & ((ev[:, 3] == RESET_ALWAYS) | ((ev[:, 3] == RESET_IF_ZERO_CONSENSUS) & (ev[:, 2] >= 0) & (ev[:, 0] >= 1))))
+    events = [tuple(int(x) for x in row) for row in ev[ok].tolist()]
+    prm = []
+    for n, p in enumerate(params):
+        q = YumaParamsC.from_buffer_copy(bytes(p))
+        if q.reset_mode != RESET_NONE and 0 <= q.reset_epoch < E:
+            all_cols = bool(q.flags & FLAG_RESET_ALL_COLUMNS)
+            if all_cols or 0 <= q.reset_index < M:
+                if q.reset_mode == RESET_ALWAYS or (not all_cols and q.reset_epoch >= 1):
+                    events.append((q.reset_epoch, n, -1 if all_cols else q.reset_index, q.reset_mode))
+        q.reset_mode, q.reset_epoch, q.reset_index = RESET_NONE, -1, 0
+        q.flags &= ~FLAG_RESET_ALL_COLUMNS
+        prm.append(q)
+    by_epoch: dict = {}
+    for t, n, c, mode in events:
+        by_epoch.setdefault(t, []).append((n, c, mode))
+    cuts = [0] + sorted(t for t in by_epoch if t > 0) + [E]
+
+    def apply(B, evs, prevC):
+        """B [N, V, M] with the columns of the events evs zeroed (prevC [N, M]: C of the epoch before)."""
+        mask = torch.zeros((N, M), dtype=torch.bool, device=dev)
+        for n, c, mode in evs:
+            if mode == RESET_ALWAYS:
+                if c < 0:
+                    mask[n, :] = True
+                else:
+                    mask[n, c] = True
+            elif prevC is not None:
+                mask[n, c] |= prevC[n, c] == 0.0
+        return B.masked_fill(mask[:, None, :], 0.0)
+
+    B = None if B_init is None else _as_dev(B_init, dev)
+    if B is not None and 0 in by_epoch:
+        B = apply(B, by_epoch[0], None)
+    parts, hist, last = [], [], None
+    names = ("Dn", "C", "I") + tuple(want)
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        if a > 0:
+            B = apply(last.B_final, by_epoch[a], last.C[-1])
+        stored = [t for t in h_epochs if a <= t < b] if want_hist else []
+        last = run(variant, prm, W[a:b], S[a:b], B, Wprev_init if a == 0 else None, want_hist=bool(stored), want=want,
+                   chunk_epochs=chunk_epochs, workspace=workspace, shared_inputs=shared_inputs,
+                   hist_stride=hist_stride if stored else 1, hist_first=stored[0] - a if stored else None)
+        parts.append({k: (getattr(last, k) if k in ("Dn", "C", "I") else last.extra[k]) for k in names})
+        if stored:
+            hist.append(last.B_hist)
+    res = {k: torch.cat([p[k] for p in parts]) for k in names}
+    res["B_final"] = last.B_final
+    V = last.B_final.shape[1]
+    if want_hist:
+        res["B_hist"] = torch.cat(hist) if hist else torch.empty((0, N, V, M), dtype=torch.float32, device=dev)
+    for k, t in (out or {}).items():  # a caller's buffers receive the chain's results
+        if t is not None and k in res:
+            res[k] = t.copy_(res[k])
+    extra = {k: res[k] for k in want}
+    extra.update(resets_path="segments", resets=None, w_path=last.extra["w_path"], hist_path="f32")
+    return RunResult(res["Dn"], res["C"], res["I"], res["B_final"], res.get("B_hist"), extra,
+                     h_epochs if want_hist else None)
+
+
 def move_from_history(hist: torch.Tensor, B_init: torch.Tensor | None) -> torch.Tensor:
     """B_move [E, N, 2] of a dense fp32 history [E, N, V, M], by the two
     expressions that define it: (hist[t] - hist[t-1]).abs().amax((-2, -1)) and
@@ -913,14 +1052,20 @@ _OUT_SHAPES = {
 }
 
 
-def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None, move=None) -> None:
+def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None, move=None,
+            resets=None) -> None:
     """The run's one launch: yuma_run_opts, yuma_run_sched under a native
     schedule, or yuma_run_watch with a native watch list (watch: the int32
     device list, B_watch and the buffer whose address the engine gets); with `capture`, their yuma_graph_create_* twins,
     the handle appended to it. head: variant, params, N, E; tail: V, M ...
     chunk_epochs. move: B_move, for yuma_run_move (its watch list may be
-    absent: NULL, 0, NULL)."""
-    if move is not None:  # yuma_run_watch's arguments, B_move after B_watch
+    absent: NULL, 0, NULL). resets: the int32 device event list [n, 4], for
+    yuma_run_resets (no schedule, watch list or B_move beside it)."""
+    if resets is not None:  # yuma_run_opts's arguments, the list and its length after `out`
+        run_fn, graph_fn = lib.yuma_run_resets, lib.yuma_graph_create_resets
+        n_ev = resets.shape[0]
+        args = head + tail[:7] + (resets.data_ptr() if n_ev else None, n_ev) + tail[7:]
+    elif move is not None:  # yuma_run_watch's arguments, B_move after B_watch
         run_fn, graph_fn = lib.yuma_run_move, lib.yuma_graph_create_move
         w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
         args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
@@ -955,7 +1100,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
         hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None,
-        watch=None, want_move: bool = False) -> RunResult:
+        watch=None, want_move: bool = False, resets=None) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -1018,8 +1163,41 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     B_move is reduced from it on the device, a requested strided and / or
     bfloat16 history is taken from it, and it is dropped unless asked for
     (extra["move_path"] == "dense"; a captured run raises EngineError
+    instead).
+    resets: bond reset events, a sequence of (epoch, scenario, column, mode)
+    tuples or an int32 tensor [n, 4]: before epoch t's update of scenario n the
+    event zeroes bond column c (-1: every column, RESET_ALWAYS only) if a bond
+    state exists (t >= 1, or B_init given) and the mode's rule holds --
+    RESET_ALWAYS always, RESET_IF_ZERO_CONSENSUS iff t >= 1 and C[t-1, n, c] ==
+    0. Duplicates and any order are allowed; the params' own reset keeps
+    working beside the events. A host sequence (or CPU tensor) is validated
+    before anything touches a GPU (ValueError); a CUDA tensor is passed through
+    unchecked, and the device code ignores an event out of range. Every output
+    has the bits of the chain of runs cut at the event epochs and resumed from
+    B_final with the columns zeroed. Yuma 3 / Yuma 4 only, and not together
+    with sched, watch, want_move, single_call or a bfloat16 history
+    (ValueError). Where resets_native holds (and the buffers have the vector
+    form's alignment) the bond scan applies the events itself
+    (yuma_run_resets, extra["resets_path"] == "native"; extra["resets"] is the
+    int32 device list a captured run re-reads at every replay -- a caller's own
+    contiguous int32 device tensor is used as it is); elsewhere (the scalar
+    form, shared inputs, uint16 weights, the full-output matrices) that chain
+    runs (extra["resets_path"] == "segments"; a captured run raises EngineError
     instead)."""
     h_bf16 = hist_dtype == torch.bfloat16
+    resets_host = None
+    if resets is not None:  # refused and validated before anything touches a GPU
+        if variant not in (VARIANT_YUMA3, VARIANT_YUMA4):
+            raise ValueError("resets= takes Yuma 3 / Yuma 4 only")
+        for name, given in (("sched", sched is not None), ("watch", watch is not None), ("want_move", bool(want_move)),
+                            ("single_call", bool(single_call)), ("hist_dtype=torch.bfloat16", h_bf16)):
+            if given:
+                raise ValueError(f"resets= does not combine with {name}")
+        if isinstance(resets, torch.Tensor) and resets.is_cuda:
+            if resets.dtype != torch.int32 or resets.dim() != 2 or resets.shape[1] != 4:
+                raise ValueError(f"a device event list must be int32 [n, 4], not {resets.dtype} {tuple(resets.shape)}")
+        else:
+            resets_host = _resets_host(resets, len(params) if shared_inputs else W.shape[1], W.shape[0], W.shape[3])
     dev, N, E, K, sched_host, h_epochs, watch_host = _check_args(
         params, W, S, B_init, Wprev_init, out, single_call=single_call, shared_inputs=shared_inputs,
         hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched, watch=watch,
@@ -1062,7 +1240,23 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
             r.extra["watch_path"], r.extra["watch"] = "dense", None
         return r
 
+    def segments():
+        """the chain of existing runs that defines the events (nothing is launched yet)"""
+        if capture is not None:
+            raise EngineError("a captured run cannot cut itself at the event epochs: resets= needs "
+                              "resets_native(variant, N, E, V, M, ...) and vector-aligned buffers")
+        if phase_ms is not None:
+            raise ValueError("phase_ms times one launch: the events of this call are not native")
+        ev = resets_host if resets_host is not None else resets.detach().to(device="cpu", dtype=torch.int64)
+        return _run_segments(variant, params, W_arg, S_arg, B_init, Wprev_init, ev, N=N, E=E, M=M, h_epochs=h_epochs,
+                             want_hist=want_hist or (out or {}).get("B_hist") is not None, want=want,
+                             chunk_epochs=chunk_epochs, workspace=workspace, out=out, shared_inputs=shared_inputs,
+                             hist_stride=hist_stride)
+
     out_names = tuple(want) + tuple(k for k, v in (out or {}).items() if v is not None and k != "B_hist")
+    if resets is not None and not resets_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs,
+                                                w_u16=W.dtype == torch.uint16):
+        return segments()
     if want_move and (want_hist or (out or {}).get("B_hist") is not None
                       or not move_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs)):
         return move_dense()
@@ -1136,6 +1330,14 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
             W, S = _take_slices(W, sched_host.to(dev)), _take_slices(S, sched_host.to(dev))
     if want_move and not _vector_form(W, w_u16, B_init, Wprev_init, o, False):  # (nothing is launched yet)
         return move_dense()
+    resets_dev = None
+    if resets is not None:
+        if not _vector_form(W, False, B_init, Wprev_init, o, False):  # (nothing is launched yet)
+            return segments()
+        if resets_host is None:
+            resets_dev = resets if resets.is_contiguous() else resets.contiguous()  # the caller's tensor, unchecked
+        else:
+            resets_dev = resets_host.to(device=dev, dtype=torch.int32)
     b_move = torch.empty((E, N, 2), dtype=torch.float32, device=dev) if want_move else None  # (the engine zeroes it)
     watch_arg = None
     if watch_host is not None and not watch_dense:
@@ -1150,6 +1352,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     full = o.get("Tv") is not None
     if sched_dev is not None:
         nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
+    elif resets_dev is not None and resets_dev.shape[0] > 0:
+        nbytes = int(lib.yuma_workspace_bytes_resets(variant, N, E, V, M, 1 if full else 0))
     else:
         nbytes = workspace_bytes(variant, N, E, V, M, full)
     if workspace is None or workspace.numel() < nbytes:
@@ -1169,7 +1373,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         _launch(lib, dev, (variant, prm.data_ptr(), N, E), K, sched_dev,
                 (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
                  workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
-                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move)
+                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move, resets=resets_dev)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -1180,6 +1384,9 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         keep["sched"] = sched_dev
     if want_move:
         keep["move_path"] = "native"
+    if resets is not None:  # how the events were applied: by the bond scan, or by cutting the run
+        keep["resets_path"] = "native"
+        keep["resets"] = resets_dev
     hist = o.get("B_hist")
     if h_bf16 and hist is not None and not hist_native:  # the fp32 history, rounded to nearest even
         hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)

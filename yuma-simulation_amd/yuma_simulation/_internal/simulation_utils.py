@@ -93,7 +93,8 @@ def _reward_key(config: YumaConfig) -> tuple:
 
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                     want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None,
-                    dedup_inputs: bool = False, bonds_columns=None, bonds_movement: bool = False):
+                    dedup_inputs: bool = False, bonds_columns=None, bonds_movement: bool = False,
+                    bond_resets=None):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
@@ -128,7 +129,19 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     and for the other versions, it is reduced from the run's history on the
     device. The first
     three elements keep the default call's bits. Combines with bonds_every,
-    bonds_dtype, dedup_inputs and bonds_columns."""
+    bonds_dtype, dedup_inputs and bonds_columns.
+    bond_resets: None, or one entry per run: None or a list of (epoch, index)
+    pairs, each applied by that run's version as the reference applies the
+    case's own reset_bonds_epoch / reset_bonds_index (simulation_utils.py:62-88):
+    Yuma 3.1 zeroes bond column `index` before epoch `epoch` unconditionally,
+    Yuma 3.2 / Yuma 4 only if the previous epoch's consensus of that miner is
+    exactly 0, every other version ignores the pairs. Any number of pairs, in
+    any order, beside the case's own pair (engine.run's resets: one engine call
+    per group still, the scenario index added). Epochs and indices are plain
+    ints, the index in [0, M) (ValueError otherwise, before anything touches a
+    GPU); an epoch outside [0, E) is never reached, as in the reference. Does
+    not combine with dedup_inputs, bonds_columns, bonds_movement or
+    bonds_dtype=torch.bfloat16 (ValueError)."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
     if bonds_dtype not in (None, torch.float32, torch.bfloat16):
@@ -141,13 +154,47 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
             if max(bonds_columns) >= M:
                 raise ValueError(f"bonds_columns: index {max(bonds_columns)} is outside run {k} "
                                  f"('{r.case.name}', {r.yuma_version}), which has M={M} miners")
+    if bond_resets is not None:  # validated on the host, before anything touches a GPU
+        bond_resets = _check_bond_resets(runs, bond_resets)
+        for name, given in (("dedup_inputs", dedup_inputs), ("bonds_columns", bonds_columns is not None),
+                            ("bonds_movement", bonds_movement), ("bonds_dtype=torch.bfloat16", bonds_dtype == torch.bfloat16)):
+            if given:
+                raise ValueError(f"bond_resets does not combine with {name}")
     # the result lists are thousands of fresh containers (the sheet: 1512
     # dividend lists): the cyclic collector would sweep the process's whole
     # heap several times while they are built; they hold no cycles
     with _no_cyclic_gc():
         return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every),
                                 bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs),
-                                bonds_columns=bonds_columns, bonds_movement=bool(bonds_movement))
+                                bonds_columns=bonds_columns, bonds_movement=bool(bonds_movement),
+                                bond_resets=bond_resets)
+
+
+def _check_bond_resets(runs, bond_resets) -> list:
+    """run_simulations' bond_resets as one list of (epoch, index) int pairs per
+    run (empty: none), epochs outside the run dropped. ValueError for anything
+    but plain ints, a negative epoch or an index outside [0, M)."""
+    if isinstance(bond_resets, (str, bytes)) or not hasattr(bond_resets, "__len__") or len(bond_resets) != len(runs):
+        raise ValueError(f"bond_resets must hold one entry (None or a list of (epoch, index) pairs) per run: "
+                         f"{len(runs)} runs")
+    out = []
+    for k, (r, pairs) in enumerate(zip(runs, bond_resets)):
+        kept = []
+        if pairs is not None:
+            E, _, M = r.case.packed_inputs()[0].shape
+            for pair in pairs:
+                if not isinstance(pair, (tuple, list)) or len(pair) != 2 or not all(type(x) is int for x in pair):
+                    raise ValueError(f"bond_resets[{k}]: {pair!r} is not an (epoch, index) pair of ints")
+                epoch, index = pair
+                if epoch < 0:
+                    raise ValueError(f"bond_resets[{k}]: epoch {epoch} is negative")
+                if not 0 <= index < M:
+                    raise ValueError(f"bond_resets[{k}]: index {index} is outside [0, M={M}) of run {k} "
+                                     f"('{r.case.name}', {r.yuma_version})")
+                if epoch < E:
+                    kept.append((epoch, index))
+        out.append(kept)
+    return out
 
 
 @contextmanager
@@ -205,7 +252,7 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
                      totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False,
-                     bonds_columns=None, bonds_movement: bool = False):
+                     bonds_columns=None, bonds_movement: bool = False, bond_resets=None):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -248,11 +295,14 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
         sched = None
         if dedup_inputs:  # the group's distinct joint slices and the schedule over them
             W, S, sched = engine.dedup_slices(W, S)
+        # the group's reset events: each run's pairs under its version's rule, with its scenario index
+        events = [(e, j, i, packed[k][1]) for j, k in enumerate(idx) if packed[k][1] != engine.RESET_NONE
+                  for e, i in (bond_resets[k] if bond_resets is not None else ())]
         watch = bonds_columns if want_bonds else None  # the watched columns in place of the [V, M] history
         launched.append((E, V, idx, S_host, engine.run(
             variant, params, W, S, want_hist=want_bonds and watch is None, hist_stride=bonds_every, sched=sched,
             hist_dtype=bonds_dtype if want_bonds and watch is None else None, watch=watch,
-            **({"want_move": True} if bonds_movement else {}))))
+            **({"want_move": True} if bonds_movement else {}), **({"resets": events} if events else {}))))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
         hist = None
