@@ -417,6 +417,66 @@ int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, in
 int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
 
 /* ------------------------------------------------------------------------
+ * Watched validator rows: the bond history of a few validators.
+ *
+ * The other half of the watch list's question: where are validator v's bonds
+ * across all miners, and which miners pay it (D[v] = sum over m of B[v][m]
+ * I[m])? yuma_run_rows takes a list rows_dev [n_rows] of validator indices in
+ * DEVICE memory and writes B_rows [n_hist][N][n_rows][M] (fp32), n_hist =
+ * yuma_hist_slots(E, stride, first) under the options' history stride and
+ * first epoch: slot s, row j holds the bits the dense history holds at
+ * [epoch t_s][n][rows_dev[j]][0 .. M). Duplicated and unsorted rows are
+ * allowed. out->B_hist may be NULL -- the intended use: the main run takes its
+ * history-less scans, and a small kernel of its own (k_bonds_rows, counted
+ * under YUMA_PHASE_BONDS) recomputes the watched rows from the per-epoch
+ * vectors phase 1 leaves in the workspace -- or non-NULL: both histories are
+ * written. YUMA_RUN_HIST_BF16 concerns B_hist only; B_rows is fp32. Every
+ * other output, B_final included, has the bits of the same run without a row
+ * list. The row list needs no workspace of its own.
+ *
+ * The arguments are yuma_run_move's with rows_dev, n_rows and B_rows after
+ * B_move. Here B_move == NULL means "no movement output" (yuma_run_move keeps
+ * refusing NULL), and n_watch == 0 with NULL watch_dev and NULL B_watch means
+ * "no watch list" as there. The row list is mandatory.
+ *
+ * Native (yuma_rows_native returns 1; host only, makes no HIP call; `flags`
+ * are the run's flags): Yuma 3 and Yuma 4 (scalar or liquid alpha, any reset
+ * of the parameter record), any V up to YUMA_MAX_VALIDATORS, any M and any
+ * alignment (four columns per thread in 16-byte accesses where M % 4 == 0 and
+ * W, B_init, the state, bond_alpha and B_rows are aligned for them; one
+ * column per thread elsewhere), no YUMA_RUN_SHARED_INPUTS; with
+ * YUMA_RUN_W_U16 where yuma_u16_native holds. Elsewhere the entry points
+ * return YUMA_EUNSUPPORTED before the first launch and the caller gathers the
+ * rows of an fp32 history itself.
+ *
+ * The host cannot check a list in device memory without a synchronisation:
+ * the kernel clamps every entry into [0, V) before it addresses anything, so a
+ * bad entry gives unspecified numbers and never an access outside a buffer. A
+ * graph re-reads the list at every replay: rewrite it in place between
+ * replays like any other input.
+ *
+ * Refusals, in this order, all before the first launch and without a HIP call
+ * (yuma_graph_create_rows: the same code and yuma_last_error text, before the
+ * capture opens): the options (as yuma_run_opts); [the graph handle]; sizes;
+ * NULL params / W / S / out / workspace; a schedule pointer with K < 1, or
+ * K != 0 without one (YUMA_EINVAL); with a watch list (n_watch != 0 or either
+ * pointer given), n_watch < 1, then a NULL watch_dev or B_watch (YUMA_EINVAL);
+ * n_rows < 1, then a NULL rows_dev or B_rows, then a grid of N n_rows
+ * ceil(M / 64) blocks beyond INT_MAX (YUMA_EINVAL); the workspace size; the
+ * schedule not native; the watch list not native; with a B_move, the movement
+ * not native, then not in vector form; the row list not native
+ * (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and YUMA_RUN_W_U16 as ever.
+ * yuma_epoch, yuma_shard_stage and the older entry points take no row list.
+ * ---------------------------------------------------------------------- */
+int yuma_run_rows(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                  const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                  const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
+                  int n_watch, float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows,
+                  float* B_rows, void* workspace, size_t workspace_bytes, int chunk_epochs,
+                  const yuma_run_options_t* opts, void* stream, float* phase_ms);
+int yuma_rows_native(int variant, int N, int E, int V, int M, int n_rows, int flags);
+
+/* ------------------------------------------------------------------------
  * Bond reset events: any number of column resets inside one run.
  *
  * A subnet deregisters miners all the time, and every deregistration clears
@@ -598,6 +658,14 @@ int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t
                            const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
                            float* B_watch, float* B_move, void* workspace, size_t workspace_bytes,
                            int chunk_epochs, const yuma_run_options_t* opts);
+/* yuma_graph_create_move with a row list (yuma_run_rows's arguments). */
+int yuma_graph_create_rows(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                           int E, int K, int V, int M, const float* W, const float* S,
+                           const int32_t* sched_dev, const float* B_init, const float* Wprev_init,
+                           const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                           float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows,
+                           float* B_rows, void* workspace, size_t workspace_bytes, int chunk_epochs,
+                           const yuma_run_options_t* opts);
 /* yuma_graph_create_opts with reset events (yuma_run_resets's arguments). */
 int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
                              int E, int V, int M, const float* W, const float* S,

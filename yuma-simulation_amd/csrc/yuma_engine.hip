@@ -4899,6 +4899,204 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_watch(WatchArgs A) {
 }
 
 // ---------------------------------------------------------------------------
+// Watched validator rows (yuma_run_rows): the bond history of a few
+// validators over every miner, every stored epoch in fp32, without a [V][M]
+// history -- k_bonds_watch's other direction, on the same grounds (Yuma 3 /
+// Yuma 4 are element-wise; the main scan keeps its code) and enqueued at the
+// same place, before the chunk's main scan.
+//   One thread owns (scenario n, watched index j, columns m .. m + C - 1), m
+//   fastest; a block is one wave of one (n, j), so the parameters, the row
+//   clamp(rows[j], 0, V - 1) and the row's sum and stake are block-uniform and
+//   the [M] row of a stored slot goes out as contiguous stores. The host
+//   cannot check device memory: a bad list gives unspecified numbers and never
+//   an access outside W or the state.
+//   C = 4: a lane's four columns are one 16-byte access (8 bytes of uint16 W)
+//   of W, the old state, the liquid bond_alpha and B_rows; launch_rows takes
+//   it when M % 4 == 0 and every one of those buffers is on that alignment.
+//   C = 1: any M and alignment, scalar accesses only. A thread whose first
+//   column is >= M (the tail of a row's last block) leaves at once: it loads
+//   and stores nothing (with C = 4, M % 4 == 0: a quad is inside or outside).
+//   Inputs of an epoch (the weights, the row's sum and stake, bond_alpha) sit
+//   in a register ring kRowsP epochs deep, every fetch unconditional with its
+//   epoch clamped to the launch's last one, as in k_bonds_watch and for the
+//   reason written there. The row's sum and stake are block-uniform: left to
+//   itself the compiler reads them with scalar loads, whose counter (lgkmcnt,
+//   out-of-order returns) can only be waited to zero, which would drain the
+//   ring's newest fetch at every epoch; the row index is therefore handed to
+//   the fetch through a vector register (an empty asm statement), so that
+//   they are vector loads in vmcnt order like the rest of the ring.
+//   Arithmetic, reset rule (per component: its own column against
+//   reset_index) and history countdown: k_bonds_watch's. Slot s goes to
+//   B_rows[s][n][j][m ..] on a test of t alone.
+// ---------------------------------------------------------------------------
+constexpr int kRowsP = 8;  // epochs of inputs in flight
+struct RowsArgs {
+  const void* W;  // fp32 or (WT = uint16_t) uint16 elements; [E][N][V][M], or [K][N][V][M] under SC
+  const float* rsd;
+  const float* sn;
+  const float* C;
+  const float* ba;
+  const yuma_params_t* prm;
+  const float* B_init;
+  const float* Bstate;   // [N][V][M], the state before epoch t0 when t0 > 0
+  const int32_t* rows;   // [nr] device memory
+  float* B_rows;         // [n_hist][N][nr][M]
+  const int32_t* sched;  // SC: [E] device memory
+  int K;                 // SC: stored slices
+  int N, V, M, nr, t0, t1;
+  int bpr;  // blocks per row
+  int hstride, hnext, hslot;
+};
+template <int VARIANT, typename WT, bool SC, int C>
+__global__ __launch_bounds__(kWatchBS) void k_bonds_rows(RowsArgs A) {
+  static_assert(VARIANT == YUMA_VARIANT_YUMA3 || VARIANT == YUMA_VARIANT_YUMA4, "element-wise variants only");
+  static_assert(C == 4 || C == 1, "a quad of columns per thread, or one");
+  constexpr int P = kRowsP;
+  constexpr bool U16 = std::is_same_v<WT, uint16_t>;
+  // a thread's weights and bond_alpha of one epoch: one vector, or one element
+  using WV = std::conditional_t<C == 4, std::conditional_t<U16, usvec4, fvec4>, WT>;
+  using FV = std::conditional_t<C == 4, fvec4, float>;
+  const int N = A.N, V = A.V, M = A.M, nr = A.nr;
+  const int nj = blockIdx.x / A.bpr;
+  const int n = nj / nr, j = nj - n * nr;
+  const long long m0 = ((long long)(blockIdx.x % A.bpr) * kWatchBS + threadIdx.x) * C;
+  if (m0 >= M) return;
+  const int m = (int)m0;
+  const int v = min(max(A.rows[j], 0), V - 1);
+  const long long VM = (long long)V * M;
+  const yuma_params_t& pg = A.prm[n];
+  const bool liquid = pg.liquid_mode != YUMA_LIQUID_OFF;
+  const int reset_mode = pg.reset_mode, reset_epoch = pg.reset_epoch, reset_index = pg.reset_index;
+  const bool reset_all = (pg.flags & YUMA_FLAG_RESET_ALL_COLUMNS) != 0;
+  const float p_bond_alpha = pg.bond_alpha, p_omba = pg.one_minus_bond_alpha;
+  const float p_maxint = pg.maxint, p_capacity_alpha = pg.capacity_alpha, p_decay_keep = pg.decay_keep;
+  // reset_c_zero's test on this record's fields
+  bool zero_c = false;
+  if (reset_mode == YUMA_RESET_IF_ZERO_CONSENSUS && !reset_all && reset_epoch >= 1 && reset_epoch >= A.t0 &&
+      reset_epoch < A.t1 && reset_index >= 0 && reset_index < M)
+    zero_c = A.C[((long long)(reset_epoch - 1) * N + n) * M + reset_index] == 0.0f;
+  const WT* const Wa = static_cast<const WT*>(A.W);
+  const long long roff = (long long)v * M + m;  // the thread's first element inside a [V][M] slice
+
+  auto comp = [](const auto& x, int c) -> float {
+    if constexpr (C == 4)
+      return wf32(x[c]);
+    else
+      return wf32(x);
+  };
+  const float* src = A.t0 == 0 ? A.B_init : A.Bstate;
+  bool has_old = src != nullptr;
+  float B[C];
+  if (has_old) {
+    const FV b0 = *reinterpret_cast<const FV*>(src + n * VM + roff);
+#pragma unroll
+    for (int c = 0; c < C; ++c) B[c] = comp(b0, c);
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) B[c] = 0.0f;
+  }
+
+  int vv = v;  // the row index of the ring's loads, in a vector register (see above)
+  asm volatile("" : "+v"(vv));
+  WV rw[P];
+  FV rba[P];
+  float rd[P], rsn[P];
+  // SC: the stored slice of epoch t, as k_bonds_watch reads it
+  auto sched_at = [&](int t) -> int {
+    if constexpr (SC) {
+      typedef const __attribute__((address_space(4))) int32_t* cptr;
+      const int tt = __builtin_amdgcn_readfirstlane(min(t, A.t1 - 1));
+      return min(max(__builtin_amdgcn_readfirstlane(((cptr)A.sched)[tt]), 0), A.K - 1);
+    } else {
+      return 0;
+    }
+  };
+  auto fetch = [&](int k, int t, int sk) {
+    const long long slice = (long long)t * N + n;
+    const long long wslice = SC ? (long long)sk * N + n : slice;
+    rw[k] = *reinterpret_cast<const WV*>(Wa + wslice * VM + roff);
+    rd[k] = A.rsd[slice * V + vv];
+    rsn[k] = A.sn[slice * V + vv];
+    // Yuma 4 reads bond_alpha for every scenario (k_bonds_watch): no branch around a load
+    if constexpr (VARIANT == YUMA_VARIANT_YUMA4) rba[k] = *reinterpret_cast<const FV*>(A.ba + slice * M + m);
+  };
+  int hnext = A.hnext;
+  long long hsl = (long long)A.hslot * N + n;
+  const int tl = A.t1 - 1;
+#pragma unroll
+  for (int k = 0; k < P; ++k) {
+    fetch(k, min(A.t0 + k, tl), sched_at(A.t0 + k));
+    // the ring fills in the order the loop empties it: left to the scheduler the first slot's loads were
+    // issued last, and the wait at the loop's head (the join with the back edge) became vmcnt(0)
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  int snext = sched_at(A.t0 + P);
+
+  // One epoch from ring slot k; FETCH: refill the slot with epoch t + P's inputs.
+  auto step = [&](int k, int t, auto FETCH) {
+    if (has_old && reset_mode != YUMA_RESET_NONE && t == reset_epoch &&
+        (reset_all || (reset_index >= 0 && reset_index < M))) {
+      bool fire = reset_mode == YUMA_RESET_ALWAYS;
+      if (reset_mode == YUMA_RESET_IF_ZERO_CONSENSUS && t >= 1 && !reset_all) fire = zero_c;
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (fire && (reset_all || reset_index == m + c)) B[c] = 0.0f;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float wn = comp(rw[k], c) / rd[k];
+      if constexpr (VARIANT == YUMA_VARIANT_YUMA3) {
+        const float cap = rsn[k] * p_maxint;
+        const float ca = p_capacity_alpha * cap;
+        const float rem = tmax(cap - B[c], 0.0f);
+        const float pc = tmin(ca, rem);
+        const float nb = p_decay_keep * B[c] + pc * wn;
+        B[c] = tmin(nb, cap);
+      } else {
+        const float a = comp(rba[k], c);
+        const float bac = liquid ? a : p_bond_alpha;
+        const float omba = liquid ? 1.0f - a : p_omba;
+        const float bd = B[c] * omba;
+        const float rem = tmax(1.0f - bd, 0.0f);
+        const float nb = bd + tmin(bac * wn, rem);
+        B[c] = tmin(nb, 1.0f);
+      }
+    }
+    if (t == hnext) {  // from t alone: the same branch in every thread
+      float* const dst = A.B_rows + (hsl * nr + j) * M + m;
+      if constexpr (C == 4)
+        *reinterpret_cast<fvec4*>(dst) = fvec4{B[0], B[1], B[2], B[3]};
+      else
+        dst[0] = B[0];
+      hnext += A.hstride;
+      hsl += N;
+    }
+    has_old = true;
+    if constexpr (decltype(FETCH)::value) {
+      fetch(k, min(t + P, tl), snext);
+      if constexpr (SC) snext = sched_at(t + P + 1);
+    }
+  };
+  // Whole groups of P epochs: no way out of the loop but its end. With the
+  // run's end tested between the steps (k_bonds_watch's form) the compiler
+  // routes each of those exits through the loop's latch, the waitcnt pass sees
+  // a way from the middle of the ring to its head, across which the first
+  // slot's loads are the newest, and waits for vmcnt(0) there: the whole ring
+  // drained once per P epochs.
+  int tb = A.t0;
+  for (; tb + P <= A.t1; tb += P) {
+#pragma unroll
+    for (int k = 0; k < P; ++k) step(k, tb + k, std::true_type{});
+  }
+  // ... and the last epochs, fewer than P, from the slots the last fetches filled: straight-line code
+#pragma unroll
+  for (int k = 0; k < P - 1; ++k) {
+    if (tb + k >= A.t1) return;
+    step(k, tb + k, std::false_type{});
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Phase 2 for parameter sweeps over ONE input trajectory (shared inputs,
 // config c3), element-wise variants: a block runs the scan of K scenarios
 // side by side over one 16 R-row x 64-miner tile of W. Every scenario of the
@@ -6181,6 +6379,55 @@ void launch_watch(hipStream_t st, int variant, const yk::BondArgs& A, const int3
   });
 }
 
+// Blocks per watched row of k_bonds_rows with c columns per thread
+long long rows_bpr(int M, int c) { return (((long long)M + c - 1) / c + yk::kWatchBS - 1) / yk::kWatchBS; }
+
+// The watched rows' scan over the chunk of A (k_bonds_rows), from the main
+// scan's own arguments like launch_watch, and enqueued before that scan too.
+// The vector form (four columns per thread) where M % 4 == 0 and W (8 bytes
+// for uint16), the old state (B_init, the state buffer), the liquid bond_alpha
+// and B_rows are on a 16-byte boundary; one column per thread elsewhere.
+template <typename WT>
+void launch_rows(hipStream_t st, int variant, const yk::BondArgs& A, const int32_t* rows, int nr, float* B_rows,
+                 const int32_t* sched, int K) {
+  yk::RowsArgs X{};
+  X.W = A.W;
+  X.rsd = A.rsd;
+  X.sn = A.sn;
+  X.C = A.C;
+  X.ba = A.ba;
+  X.prm = A.prm;
+  X.B_init = A.B_init;
+  X.Bstate = A.Bstate;
+  X.rows = rows;
+  X.B_rows = B_rows;
+  X.sched = sched;
+  X.K = K;
+  X.N = A.N;
+  X.V = A.V;
+  X.M = A.M;
+  X.nr = nr;
+  X.t0 = A.t0;
+  X.t1 = A.t1;
+  X.hstride = A.hstride;
+  X.hnext = A.hnext;
+  X.hslot = A.hslot;
+  const bool quad = (A.M % 4) == 0 && ((uintptr_t)A.W & (4 * sizeof(WT) - 1)) == 0 && aligned16(A.B_init) &&
+                    aligned16(A.Bstate) && aligned16(A.ba) && aligned16(B_rows);
+  X.bpr = (int)rows_bpr(A.M, quad ? 4 : 1);
+  const long long nblocks = (long long)A.N * nr * X.bpr;
+  with_bool(sched != nullptr, [&](auto SC) {
+    constexpr bool kSc = decltype(SC)::value;
+    with_bool(quad, [&](auto QUAD) {
+      constexpr int kC = decltype(QUAD)::value ? 4 : 1;
+      if (variant == YUMA_VARIANT_YUMA3)
+        YK_LAUNCH((yk::k_bonds_rows<YUMA_VARIANT_YUMA3, WT, kSc, kC>), nblocks, yk::kWatchBS, st, X);
+      else
+        YK_LAUNCH((yk::k_bonds_rows<YUMA_VARIANT_YUMA4, WT, kSc, kC>), nblocks, yk::kWatchBS, st, X);
+    });
+  });
+}
+
 // Optional per-phase timing (bench / roofline): a HIP event is recorded on the
 // launch stream at every phase boundary, labelled with the phase that starts
 // there; each segment's elapsed time goes to its label.
@@ -6249,6 +6496,18 @@ bool sched_native(int variant, int N, int E, int K, int V, int M, const yuma_out
 bool watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags) {
   if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
   if (N < 1 || E < 1 || V < 1 || M < 1 || n_watch < 1 || V > YUMA_MAX_VALIDATORS) return false;
+  if (flags & YUMA_RUN_SHARED_INPUTS) return false;
+  if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, nullptr, flags)) return false;
+  return true;
+}
+
+// Whether a run with these arguments writes a watched-row history natively
+// (yuma_rows_native): the element-wise variants, per-scenario inputs. The
+// kernel has a scalar form: any M, any alignment, any validator count. With
+// YUMA_RUN_W_U16 in `flags`, where the uint16 weights are native.
+bool rows_native(int variant, int N, int E, int V, int M, int n_rows, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || V < 1 || M < 1 || n_rows < 1 || V > YUMA_MAX_VALIDATORS) return false;
   if (flags & YUMA_RUN_SHARED_INPUTS) return false;
   if ((flags & YUMA_RUN_W_U16) && !u16_native(variant, N, E, V, M, nullptr, flags)) return false;
   return true;
@@ -6423,6 +6682,12 @@ struct RunReq {
   // (n_watch = 0 with NULL watch / B_watch: has_watch stays 0)
   int has_move = 0;
   float* B_move = nullptr;
+  // yuma_run_rows (has_rows): the watched validator rows rows[n_rows] (device memory) and their history
+  // B_rows [n_hist][N][n_rows][M]; its watch list may be empty and its B_move NULL (has_move stays 0)
+  int has_rows = 0;
+  const int32_t* rows = nullptr;
+  int n_rows = 0;
+  float* B_rows = nullptr;
   // yuma_run_resets (has_resets): the events events[n_events] (device memory); n_events = 0 with a NULL list
   // leaves has_resets 0, the run yuma_run_opts makes
   int has_resets = 0;
@@ -6525,6 +6790,11 @@ int check_native(const RunReq& q, bool vec, bool sched, int K) {
                   "the bond movement (yuma_move_native) needs the vector form: W vector-aligned and the fp32 "
                   "matrices 16-byte aligned");
   }
+  if (q.has_rows && !rows_native(variant, N, E, V, M, q.n_rows, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
+    return fail(YUMA_EUNSUPPORTED,
+                "a row list is not native for variant=%d V=%d shared=%d (yuma_rows_native): run the fp32 "
+                "history and gather the rows",
+                variant, V, wsh);
   if (q.hist_bf16) {
     if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
     if (!hist_bf16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
@@ -6587,6 +6857,13 @@ int run_plan(const RunReq& q, RunPlan* p) {
       return fail(YUMA_EINVAL, "n_watch=%d: N V n_watch elements exceed the watch kernel's grid", q.n_watch);
   }
   if (q.has_move && q.B_move == nullptr) return fail(YUMA_EINVAL, "B_move is NULL");
+  if (q.has_rows) {
+    if (q.n_rows < 1) return fail(YUMA_EINVAL, "n_rows=%d watched rows: at least one is required", q.n_rows);
+    if (q.rows == nullptr || q.B_rows == nullptr) return fail(YUMA_EINVAL, "the row list or B_rows is NULL");
+    // (k_bonds_rows: one wave per block, N n_rows blocks-per-row blocks; the scalar form has the most)
+    if (rows_bpr(M, 1) * q.n_rows * N > INT_MAX)
+      return fail(YUMA_EINVAL, "n_rows=%d: N n_rows M elements exceed the row kernel's grid", q.n_rows);
+  }
   if (q.n_events < 0) return fail(YUMA_EINVAL, "n_events=%d must not be negative", q.n_events);
   if (q.n_events > 0 && q.events == nullptr) return fail(YUMA_EINVAL, "n_events=%d with a NULL event list", q.n_events);
   const int full = out->Tv != nullptr;
@@ -6795,6 +7072,8 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     tm.mark(YUMA_PHASE_BONDS);
     if (q.has_watch)  // (Yuma 3 / Yuma 4: run_plan) the state before epoch c0 is still in A.Bstate
       launch_watch<WT>(st, variant, A, q.watch, q.n_watch, q.B_watch, sched, K);
+    if (q.has_rows)  // (likewise)
+      launch_rows<WT>(st, variant, A, q.rows, q.n_rows, q.B_rows, sched, K);
     const ScanPlan scan = plan_scan(scan_key(q, vec, sched != nullptr, true, yk::hist_strided(A)));
     launch_scan(st, scan, A, sched, K, q.B_move, rmask);
     const int ptiles = scan.ptiles;
@@ -7222,6 +7501,18 @@ void read_move(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_
   q->B_move = B_move;
 }
 
+// yuma_run_rows / yuma_graph_create_rows: as read_move, but a NULL B_move is "no movement output"; and the row
+// list as given (run_plan refuses what is wrong with it).
+void read_rows(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
+               const int32_t* rows_dev, int n_rows, float* B_rows, RunReq* q) {
+  read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, q);
+  if (B_move == nullptr) q->has_move = 0;
+  q->has_rows = 1;
+  q->rows = rows_dev;
+  q->n_rows = n_rows;
+  q->B_rows = B_rows;
+}
+
 // yuma_run_resets / yuma_graph_create_resets: the event list as given (run_plan refuses what is wrong with it);
 // n_events = 0 with a NULL list is "no events", the run of yuma_run_opts.
 void read_resets(const yuma_reset_event_t* events_dev, int n_events, RunReq* q) {
@@ -7357,6 +7648,19 @@ int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, in
   return run_direct(q);
 }
 
+int yuma_run_rows(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                  const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                  const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                  float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows, float* B_rows, void* workspace,
+                  size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts, void* stream,
+                  float* phase_ms) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, &q);
+  return run_direct(q);
+}
+
 size_t yuma_workspace_bytes_resets(int variant, int N, int E, int V, int M, int full_outputs) {
   if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
   return reset_table_offset(carve(nullptr, variant, N, E, V, M, full_outputs).bytes) + reset_table_bytes(N, E, M);
@@ -7380,6 +7684,10 @@ int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outpu
 
 int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
   return move_native(variant, N, E, V, M, out, flags) ? 1 : 0;
+}
+
+int yuma_rows_native(int variant, int N, int E, int V, int M, int n_rows, int flags) {
+  return rows_native(variant, N, E, V, M, n_rows, flags) ? 1 : 0;
 }
 
 int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int flags) {
@@ -7512,6 +7820,19 @@ int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t
            chunk_epochs, nullptr, nullptr};
   if (const int err = read_opts(opts, &q)) return err;
   read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, &q);
+  return graph_create_impl(graph, q);
+}
+
+int yuma_graph_create_rows(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
+                           int K, int V, int M, const float* W, const float* S, const int32_t* sched_dev,
+                           const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                           const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
+                           const int32_t* rows_dev, int n_rows, float* B_rows, void* workspace,
+                           size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, &q);
   return graph_create_impl(graph, q);
 }
 

@@ -57,6 +57,9 @@ EXPORTED_SYMBOLS = (
     "yuma_run_move",
     "yuma_move_native",
     "yuma_graph_create_move",
+    "yuma_run_rows",
+    "yuma_rows_native",
+    "yuma_graph_create_rows",
     "yuma_workspace_bytes_resets",
     "yuma_run_resets",
     "yuma_resets_native",
@@ -257,6 +260,16 @@ def load_library(path: str | None = None):
             lib.yuma_graph_create_move.restype = i32
             lib.yuma_move_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
             lib.yuma_move_native.restype = i32
+        # watched rows: yuma_run_move's arguments with the row list, its length and B_rows after B_move
+        if hasattr(lib, "yuma_run_rows"):  # (A/B libraries of older sources lack them)
+            a = lib.yuma_run_move.argtypes
+            lib.yuma_run_rows.argtypes = a[:17] + [vp, i32, vp] + a[17:]
+            lib.yuma_run_rows.restype = i32
+            a = lib.yuma_graph_create_move.argtypes
+            lib.yuma_graph_create_rows.argtypes = a[:18] + [vp, i32, vp] + a[18:]
+            lib.yuma_graph_create_rows.restype = i32
+            lib.yuma_rows_native.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+            lib.yuma_rows_native.restype = i32
         # reset events: yuma_run_opts's arguments, the list and its length after `out`
         if hasattr(lib, "yuma_run_resets"):  # (A/B libraries of older sources lack them)
             a = lib.yuma_run_opts.argtypes
@@ -538,6 +551,8 @@ class RunResult:
     B_watch: torch.Tensor | None = None         # [len(hist_epochs), N, V, len(watch_cols)] (run(watch=))
     watch_cols: tuple[int, ...] | None = None   # the miner column of each B_watch column
     B_move: torch.Tensor | None = None          # [E, N, 2]: max |B_t - B_{t-1}|, max |B_t| (run(want_move=True))
+    B_rows: torch.Tensor | None = None          # [len(hist_epochs), N, len(watch_rows), M] (run(watch_rows=))
+    watch_rows: tuple[int, ...] | None = None   # the validator row of each B_rows row
 
 
 def _as_dev(x: torch.Tensor, dev) -> torch.Tensor:
@@ -602,6 +617,17 @@ def watch_native(variant: int, N: int, E: int, V: int, M: int, n_watch: int, *, 
     `run` writes an fp32 history and gathers the columns, and RunGraph refuses."""
     flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
     return bool(load_library().yuma_watch_native(variant, N, E, V, M, n_watch, flags))
+
+
+def rows_native(variant: int, N: int, E: int, V: int, M: int, n_rows: int, *, shared_inputs: bool = False,
+                w_u16: bool = False) -> bool:
+    """Whether `run(..., watch_rows=)` with these arguments has the engine write
+    the watched rows' history itself (yuma_rows_native; needs the library, not a
+    GPU): Yuma 3 / Yuma 4, any V, any M and alignment, no shared inputs; with
+    w_u16, where u16_native holds too. Otherwise `run` writes an fp32 history
+    and gathers the rows, and RunGraph refuses."""
+    flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+    return bool(load_library().yuma_rows_native(variant, N, E, V, M, n_rows, flags))
 
 
 def move_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False,
@@ -837,20 +863,21 @@ def scan_plan(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = Fa
                     grid=p.grid, block=p.block, ptiles=p.ptiles, dpl=DP_LAYOUTS[p.dpl])
 
 
-def _watch_host(watch, M: int | None, name: str = "watch") -> torch.Tensor:
+def _watch_host(watch, M: int | None, name: str = "watch", what: str = "miner", dim: str = "M") -> torch.Tensor:
     """The watch list as a CPU int64 tensor, validated on the host: integers,
     one dimension, at least one column, every entry in [0, M) (M None: not
-    negative). ValueError otherwise."""
+    negative). ValueError otherwise. what, dim: the words of the messages (a
+    list of validator rows is checked against V)."""
     t = watch if isinstance(watch, torch.Tensor) else torch.as_tensor(np.asarray(watch))
     if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise ValueError(f"{name} must hold integer miner indices, not {t.dtype}")
+        raise ValueError(f"{name} must hold integer {what} indices, not {t.dtype}")
     if t.dim() != 1 or t.numel() < 1:
-        raise ValueError(f"{name} must be a non-empty one-dimensional list of miner indices, not shape "
+        raise ValueError(f"{name} must be a non-empty one-dimensional list of {what} indices, not shape "
                          f"{tuple(t.shape)}")
     h = t.detach().to(device="cpu", dtype=torch.int64)
     lo, hi = int(h.min()), int(h.max())
     if lo < 0 or (M is not None and hi >= M):
-        raise ValueError(f"{name} entries must lie in [0, M{'' if M is None else '=' + str(M)}): found "
+        raise ValueError(f"{name} entries must lie in [0, {dim}{'' if M is None else '=' + str(M)}): found "
                          f"{lo if lo < 0 else hi}")
     return h
 
@@ -1053,15 +1080,22 @@ _OUT_SHAPES = {
 
 
 def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None, move=None,
-            resets=None) -> None:
+            resets=None, rows=None) -> None:
     """The run's one launch: yuma_run_opts, yuma_run_sched under a native
     schedule, or yuma_run_watch with a native watch list (watch: the int32
     device list, B_watch and the buffer whose address the engine gets); with `capture`, their yuma_graph_create_* twins,
     the handle appended to it. head: variant, params, N, E; tail: V, M ...
     chunk_epochs. move: B_move, for yuma_run_move (its watch list may be
     absent: NULL, 0, NULL). resets: the int32 device event list [n, 4], for
-    yuma_run_resets (no schedule, watch list or B_move beside it)."""
-    if resets is not None:  # yuma_run_opts's arguments, the list and its length after `out`
+    yuma_run_resets (no schedule, watch list or B_move beside it). rows: the
+    int32 device row list, B_rows and the buffer whose address the engine gets,
+    for yuma_run_rows (its watch list and B_move may both be absent)."""
+    if rows is not None:  # yuma_run_move's arguments (B_move may be NULL), the row list after B_move
+        run_fn, graph_fn = lib.yuma_run_rows, lib.yuma_graph_create_rows
+        w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
+        args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
+                + w + (_ptr(move),) + (rows[0].data_ptr(), rows[0].numel(), rows[2].data_ptr()) + tail[7:])
+    elif resets is not None:  # yuma_run_opts's arguments, the list and its length after `out`
         run_fn, graph_fn = lib.yuma_run_resets, lib.yuma_graph_create_resets
         n_ev = resets.shape[0]
         args = head + tail[:7] + (resets.data_ptr() if n_ev else None, n_ev) + tail[7:]
@@ -1100,7 +1134,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
         hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None,
-        watch=None, want_move: bool = False, resets=None) -> RunResult:
+        watch=None, want_move: bool = False, resets=None, watch_rows=None) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -1183,13 +1217,33 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     contiguous int32 device tensor is used as it is); elsewhere (the scalar
     form, shared inputs, uint16 weights, the full-output matrices) that chain
     runs (extra["resets_path"] == "segments"; a captured run raises EngineError
-    instead)."""
+    instead).
+    watch_rows: a non-empty sequence or integer tensor of validator indices
+    (duplicates and any order allowed; validated on the host, ValueError): the
+    result's B_rows [n_hist, N, len(watch_rows), M] is the fp32 bond history of
+    those validators' rows alone, bit-equal to B_hist[:, :, watch_rows, :] of
+    the run without a row list, at the epochs hist_stride / hist_first select
+    (RunResult.hist_epochs; RunResult.watch_rows names the rows). Like watch=,
+    it lets the main run take the history-less scans; it combines with
+    hist_stride / hist_first, sched, uint16 W, watch, want_move, want_hist
+    (both histories are written), B_init and chunk_epochs, and not with
+    resets= (ValueError). Where rows_native holds the engine writes B_rows
+    itself (yuma_run_rows, extra["rows_path"] == "native"; extra["watch_rows"]
+    is the int32 device list a captured run re-reads at every replay -- a
+    caller's own contiguous int32 device tensor is used as it is); elsewhere
+    (Yuma 0 / 1 / 2, shared inputs, single_call) the run writes an fp32
+    history, the rows are gathered from it on the device and the history is
+    dropped unless asked for (extra["rows_path"] == "dense"; a captured run
+    raises EngineError instead)."""
     h_bf16 = hist_dtype == torch.bfloat16
+    # the row list, validated before anything touches a GPU
+    rows_host = None if watch_rows is None else _watch_host(watch_rows, W.shape[2], "watch_rows", "validator", "V")
     resets_host = None
     if resets is not None:  # refused and validated before anything touches a GPU
         if variant not in (VARIANT_YUMA3, VARIANT_YUMA4):
             raise ValueError("resets= takes Yuma 3 / Yuma 4 only")
-        for name, given in (("sched", sched is not None), ("watch", watch is not None), ("want_move", bool(want_move)),
+        for name, given in (("sched", sched is not None), ("watch_rows", watch_rows is not None),
+                            ("watch", watch is not None), ("want_move", bool(want_move)),
                             ("single_call", bool(single_call)), ("hist_dtype=torch.bfloat16", h_bf16)):
             if given:
                 raise ValueError(f"resets= does not combine with {name}")
@@ -1238,6 +1292,11 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
             r.watch_cols = tuple(int(c) for c in watch_host.tolist())
             r.hist_epochs = h_epochs
             r.extra["watch_path"], r.extra["watch"] = "dense", None
+        if rows_host is not None:
+            r.B_rows = dense.index_select(0, slots).index_select(2, rows_host.to(dev)).contiguous()
+            r.watch_rows = tuple(int(c) for c in rows_host.tolist())
+            r.hist_epochs = h_epochs
+            r.extra["rows_path"], r.extra["watch_rows"] = "dense", None
         return r
 
     def segments():
@@ -1266,8 +1325,14 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     if watch_dense and capture is not None:
         raise EngineError("a captured run cannot gather a dense history: watch= needs "
                           "watch_native(variant, N, E, V, M, n_watch)")
+    # ... and so does a row list
+    rows_dense = rows_host is not None and (
+        single_call or not rows_native(variant, N, E, V, M, rows_host.numel(), shared_inputs=shared_inputs))
+    if rows_dense and capture is not None:
+        raise EngineError("a captured run cannot gather a dense history: watch_rows= needs "
+                          "rows_native(variant, N, E, V, M, n_rows)")
     hist_asked = want_hist or (out or {}).get("B_hist") is not None
-    if watch_dense and not hist_asked:
+    if (watch_dense or rows_dense) and not hist_asked:
         want_hist, hist_dtype, h_bf16 = True, None, False  # (dropped again below)
     # uint16 weights stay 16-bit on the device where the engine reads them
     # natively (u16_native); anywhere else they are widened like any dtype
@@ -1349,6 +1414,16 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         b_watch = torch.empty((len(h_epochs), N, V, watch_host.numel()), dtype=torch.float32, device=dev)
         # (no stored epoch: nothing is written, but the engine refuses a null B_watch)
         watch_arg = (watch_dev, b_watch, b_watch if h_epochs else torch.empty(1, dtype=torch.float32, device=dev))
+    rows_arg = None
+    if rows_host is not None and not rows_dense:
+        if (isinstance(watch_rows, torch.Tensor) and watch_rows.device == dev and watch_rows.dtype == torch.int32
+                and watch_rows.is_contiguous()):
+            rows_dev = watch_rows  # the caller's tensor: a captured run follows its in-place updates
+        else:
+            rows_dev = rows_host.to(device=dev, dtype=torch.int32)
+        b_rows = torch.empty((len(h_epochs), N, rows_host.numel(), M), dtype=torch.float32, device=dev)
+        # (no stored epoch: nothing is written, but the engine refuses a null B_rows)
+        rows_arg = (rows_dev, b_rows, b_rows if h_epochs else torch.empty(4, dtype=torch.float32, device=dev))
     full = o.get("Tv") is not None
     if sched_dev is not None:
         nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
@@ -1373,7 +1448,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         _launch(lib, dev, (variant, prm.data_ptr(), N, E), K, sched_dev,
                 (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
                  workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
-                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move, resets=resets_dev)
+                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move, resets=resets_dev, rows=rows_arg)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -1390,19 +1465,28 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     hist = o.get("B_hist")
     if h_bf16 and hist is not None and not hist_native:  # the fp32 history, rounded to nearest even
         hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)
-    if watch_host is None:
+    if watch_host is None and rows_host is None:
         return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs,
                          B_move=b_move)
-    keep["watch_path"] = "dense" if watch_dense else "native"
-    if watch_dense:  # the columns of the run's fp32 history (o: before any bfloat16 conversion)
-        b_watch = o["B_hist"].index_select(3, watch_host.to(dev)).contiguous()
-        keep["watch"] = None
-        if not hist_asked:
-            hist = None
+    if (watch_dense or rows_dense) and not hist_asked:  # the history was the run's own: dropped
+        hist = None
+    if watch_host is None:
+        b_watch = None
     else:
-        keep["watch"] = watch_dev
+        keep["watch_path"] = "dense" if watch_dense else "native"
+        keep["watch"] = None if watch_dense else watch_dev
+        if watch_dense:  # the columns of the run's fp32 history (o: before any bfloat16 conversion)
+            b_watch = o["B_hist"].index_select(3, watch_host.to(dev)).contiguous()
+    if rows_host is None:
+        b_rows = None
+    else:
+        keep["rows_path"] = "dense" if rows_dense else "native"
+        keep["watch_rows"] = None if rows_dense else rows_dev
+        if rows_dense:  # the rows of the run's fp32 history
+            b_rows = o["B_hist"].index_select(2, rows_host.to(dev)).contiguous()
     return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, h_epochs, b_watch,
-                     tuple(int(c) for c in watch_host.tolist()), B_move=b_move)
+                     None if watch_host is None else tuple(int(c) for c in watch_host.tolist()), B_move=b_move,
+                     B_rows=b_rows, watch_rows=None if rows_host is None else tuple(int(c) for c in rows_host.tolist()))
 
 
 class RunGraph:

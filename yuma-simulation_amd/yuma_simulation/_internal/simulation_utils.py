@@ -94,7 +94,7 @@ def _reward_key(config: YumaConfig) -> tuple:
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                     want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None,
                     dedup_inputs: bool = False, bonds_columns=None, bonds_movement: bool = False,
-                    bond_resets=None):
+                    bond_resets=None, bonds_validators=None):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
@@ -140,8 +140,16 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     per group still, the scenario index added). Epochs and indices are plain
     ints, the index in [0, M) (ValueError otherwise, before anything touches a
     GPU); an epoch outside [0, E) is never reached, as in the reference. Does
-    not combine with dedup_inputs, bonds_columns, bonds_movement or
-    bonds_dtype=torch.bfloat16 (ValueError)."""
+    not combine with dedup_inputs, bonds_columns, bonds_validators,
+    bonds_movement or bonds_dtype=torch.bfloat16 (ValueError).
+    bonds_validators: a non-empty sequence of validator indices, valid for
+    every run of the call (ValueError names the first run whose V is too
+    small): each run's bonds list then holds [len(bonds_validators), M]
+    tensors, the default's `[bonds_validators, :]` bit for bit -- the
+    validators a study follows over every miner. The engine then keeps no
+    [V, M] history (engine.run's watch_rows). Combines with bonds_every,
+    dedup_inputs, bonds_movement and bonds_dtype as bonds_columns does; not
+    with bonds_columns (one list, one shape) nor bond_resets (ValueError)."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
     if bonds_dtype not in (None, torch.float32, torch.bfloat16):
@@ -154,6 +162,18 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
             if max(bonds_columns) >= M:
                 raise ValueError(f"bonds_columns: index {max(bonds_columns)} is outside run {k} "
                                  f"('{r.case.name}', {r.yuma_version}), which has M={M} miners")
+    if bonds_validators is not None:  # validated on the host, before anything touches a GPU
+        if bonds_columns is not None:
+            raise ValueError("bonds_validators does not combine with bonds_columns: one list, one shape of the bonds")
+        if bond_resets is not None:
+            raise ValueError("bond_resets does not combine with bonds_validators")
+        rows = engine._watch_host(bonds_validators, None, "bonds_validators", "validator", "V")
+        bonds_validators = tuple(int(c) for c in rows.tolist())
+        for k, r in enumerate(runs):
+            V = r.case.packed_inputs()[0].shape[-2]
+            if max(bonds_validators) >= V:
+                raise ValueError(f"bonds_validators: index {max(bonds_validators)} is outside run {k} "
+                                 f"('{r.case.name}', {r.yuma_version}), which has V={V} validators")
     if bond_resets is not None:  # validated on the host, before anything touches a GPU
         bond_resets = _check_bond_resets(runs, bond_resets)
         for name, given in (("dedup_inputs", dedup_inputs), ("bonds_columns", bonds_columns is not None),
@@ -167,7 +187,7 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
         return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every),
                                 bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs),
                                 bonds_columns=bonds_columns, bonds_movement=bool(bonds_movement),
-                                bond_resets=bond_resets)
+                                bond_resets=bond_resets, bonds_validators=bonds_validators)
 
 
 def _check_bond_resets(runs, bond_resets) -> list:
@@ -252,7 +272,7 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
                      totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False,
-                     bonds_columns=None, bonds_movement: bool = False, bond_resets=None):
+                     bonds_columns=None, bonds_movement: bool = False, bond_resets=None, bonds_validators=None):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -299,15 +319,20 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
         events = [(e, j, i, packed[k][1]) for j, k in enumerate(idx) if packed[k][1] != engine.RESET_NONE
                   for e, i in (bond_resets[k] if bond_resets is not None else ())]
         watch = bonds_columns if want_bonds else None  # the watched columns in place of the [V, M] history
+        rows = bonds_validators if want_bonds else None  # ... or the watched validator rows
+        dense = want_bonds and watch is None and rows is None
         launched.append((E, V, idx, S_host, engine.run(
-            variant, params, W, S, want_hist=want_bonds and watch is None, hist_stride=bonds_every, sched=sched,
-            hist_dtype=bonds_dtype if want_bonds and watch is None else None, watch=watch,
+            variant, params, W, S, want_hist=dense, hist_stride=bonds_every, sched=sched,
+            hist_dtype=bonds_dtype if dense else None, watch=watch,
+            **({"watch_rows": rows} if rows is not None else {}),
             **({"want_move": True} if bonds_movement else {}), **({"resets": events} if events else {}))))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
         hist = None
         if want_bonds and bonds_columns is not None:
             hist = res.B_watch.to(torch.bfloat16).cpu() if bonds_dtype == torch.bfloat16 else res.B_watch.cpu()
+        elif want_bonds and bonds_validators is not None:
+            hist = res.B_rows.to(torch.bfloat16).cpu() if bonds_dtype == torch.bfloat16 else res.B_rows.cpu()
         elif want_bonds:
             hist = res.B_hist.cpu()
         inc = res.I.cpu() if want_incentives else None
