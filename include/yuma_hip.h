@@ -550,6 +550,69 @@ int yuma_run_resets(int variant, const yuma_params_t* params_dev, int N, int E, 
 int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
 
 /* ------------------------------------------------------------------------
+ * Validator-row events: bond rows zeroed at any epoch inside one run.
+ *
+ * A validator that leaves or whose hotkey is replaced has its bond row
+ * cleared. yuma_run_events is yuma_run_resets with a second list,
+ * row_events_dev [n_row_events] of yuma_row_event_t in DEVICE memory, after
+ * n_events. A row event (epoch t, scenario n, row v) applies B[n][v][:] = 0
+ * before epoch t's update of scenario n, if a bond state exists (t >= 1, or
+ * t == 0 and B_init is given):
+ *  - the event is unconditional: no consensus rule applies to a validator;
+ *  - duplicates are allowed and the order does not matter; row events commute
+ *    with the column events of the same epoch (both store +0);
+ *  - an event whose epoch is outside [0, E), scenario outside [0, N), row
+ *    outside [0, V) or reserved word non-zero is ignored by the device code
+ *    and never causes an access outside a buffer;
+ *  - the column events and the scenario's own reset in yuma_params_t keep
+ *    working beside the row events.
+ * The history holds the state after the update, so a row reset at t shows in
+ * slot t, and Dn[t][n][v] is the dividend of the fresh row. Every output has
+ * the bits of the chain of yuma_run_opts calls cut at the event epochs, each
+ * resumed from the previous B_final with the rows and columns zeroed; the
+ * result does not depend on chunk_epochs.
+ *
+ * n_row_events == 0 with a NULL list is exactly yuma_run_resets: the same
+ * launches and the same workspace requirement (with n_events == 0 and a NULL
+ * list as well, yuma_run_opts's). Otherwise the workspace is
+ * yuma_workspace_bytes_events (>= yuma_workspace_bytes_resets): the difference
+ * is the row table, one 32-BIT WORD per (epoch, scenario, validator), words
+ * [E][N][V] -- the index of the scan's other per-row inputs -- padded to 256
+ * bytes, behind the column table. Zero keeps the row; the resolve kernel (one
+ * thread per event, every field range-checked before anything is addressed)
+ * sets every bit of the word with an integer atomic OR. The engine zeroes both
+ * tables with a small kernel, so inside a captured graph every replay starts
+ * from zero and re-reads both lists. The bond scan with both tables loads the
+ * R words of a lane's R rows beside the column byte, first in its fetch, and
+ * clears row i with an AND mask, branch-free; a run without column events
+ * runs it on an all-zero column table.
+ *
+ * Native (yuma_events_native, host only, no HIP call): exactly the set of
+ * yuma_resets_native. Refusals are yuma_run_resets's, in its order, with two
+ * inserted after the column list's checks: n_row_events < 0, then
+ * n_row_events > 0 with a NULL list (YUMA_EINVAL); and one appended at the end:
+ * N * V >= 2^29 with a row list (YUMA_EUNSUPPORTED: the scan steps through the
+ * row table by one epoch's N * V words as a 32-bit count of bytes; such a run's
+ * row table alone exceeds 2 GiB per epoch). All come before the first
+ * launch and without a HIP call (yuma_graph_create_events: the same code and
+ * yuma_last_error text, before the capture opens).
+ * ---------------------------------------------------------------------- */
+typedef struct yuma_row_event {
+  int32_t epoch;    /* the reset precedes this epoch's update */
+  int32_t scenario; /* 0 <= scenario < N                      */
+  int32_t row;      /* validator row, 0 <= row < V            */
+  int32_t reserved; /* must be 0                              */
+} yuma_row_event_t; /* 16 bytes */
+size_t yuma_workspace_bytes_events(int variant, int N, int E, int V, int M, int full_outputs);
+int yuma_run_events(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
+                    const float* W, const float* S, const float* B_init, const float* Wprev_init,
+                    const yuma_outputs_t* out, const yuma_reset_event_t* events_dev, int n_events,
+                    const yuma_row_event_t* row_events_dev, int n_row_events,
+                    void* workspace, size_t workspace_bytes, int chunk_epochs,
+                    const yuma_run_options_t* opts, void* stream, float* phase_ms);
+int yuma_events_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
+
+/* ------------------------------------------------------------------------
  * Which bond scan a call reaches. Host only, needs no GPU and makes no HIP
  * call: the engine's own choice (the function its runs call before they launch
  * the scan), reported for the first chunk of yuma_run_opts / yuma_run_sched
@@ -671,6 +734,13 @@ int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params
                              int E, int V, int M, const float* W, const float* S,
                              const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                              const yuma_reset_event_t* events_dev, int n_events, void* workspace,
+                             size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts);
+/* yuma_graph_create_resets with validator-row events (yuma_run_events's arguments). */
+int yuma_graph_create_events(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                             int E, int V, int M, const float* W, const float* S,
+                             const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                             const yuma_reset_event_t* events_dev, int n_events,
+                             const yuma_row_event_t* row_events_dev, int n_row_events, void* workspace,
                              size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts);
 /* Replay on `stream` (stream-ordered, no host synchronisation). */
 int yuma_graph_launch(yuma_graph_t graph, void* stream);

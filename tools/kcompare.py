@@ -55,6 +55,10 @@ def kernels(lib, every=False):
 
 
 def key(name):
+    # <..., SC, MV, RW = false, RL> takes ElemArgs<SC, MV, RW, RL>: the name of before the validator-row events (RW =
+    # true, BondArgsRw: only in a library that has them)
+    name = re.sub(r"Lb0E(Lb[01])EEEvNSt11conditionalIXT8_ENS_10BondArgsRwENS3_IXT9_ENS_10BondArgsRlE(.*)E4typeE$",
+                  r"\1EEEvNSt11conditionalIXT8_ENS_10BondArgsRlE\2", name)
     # <..., SC, MV, RL = false> takes ElemArgs<SC, MV, RL>: the name of before the reset events (RL = true,
     # BondArgsRl: only in a library that has them)
     name = re.sub(r"Lb0EEEvNSt11conditionalIXT8_ENS_10BondArgsRlENS3_IXT7_ENS3_IXT6_ENS_12BondArgsScMvENS_10BondArgsMvEE"

@@ -1,12 +1,16 @@
-"""The vector-memory waits of k_bonds_elem's RL (reset event) forms beside their
-plain twins, from the library's gfx950 code object (no GPU needed): for each
-pair the s_waitcnt vmcnt(N) instructions inside the epoch loop (the largest
-backward-branch range of the kernel and the out-of-line blocks that branch
-back into it) and outside it, the byte loads of the
-reset table, and the register report (VGPRs, SGPRs, spills, scratch).
-    python tools/kwaits.py [libyuma_hip.so] > profiles/resets/waitcnt.txt
+"""The vector-memory waits of k_bonds_elem's event forms, from the library's
+gfx950 code object (no GPU needed): the RL (reset event) forms beside their
+plain twins, and the RW (validator-row event) forms beside their RL twins.
+For each pair it prints the s_waitcnt vmcnt(N) instructions inside the epoch
+loop and outside it, the byte and dword loads, and the register report (VGPRs,
+SGPRs, spills, scratch). The epoch loop is the largest backward-branch range
+of the kernel (a conditional branch closes it; an unconditional one where
+the exit test stands at the loop's head), with the out-of-line blocks that
+branch back into it.
+    python tools/kwaits.py [libyuma_hip.so] > profiles/row_resets/waitcnt.txt
 A prefetch ring that is intact shows counted waits (vmcnt(N), N > 0) in the
-loop; a vmcnt(0) in the loop that the twin lacks is a drain."""
+loop; a vmcnt(0) in the loop that the twin lacks is a drain. A pair printed
+with `loop [-]` has no loop the tool could find and must be read by hand."""
 import collections
 import os
 import re
@@ -18,6 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kcompare  # noqa: E402
 
 RL_TAIL = "Lb1EEEvNSt11conditionalIXT8"
+# <.., RW = true, RL = false>: the row-event forms (the scan with both tables), each beside its RL twin
+RW_TAIL, RW_TWIN = "Lb1ELb0EEEvNSt11conditionalIXT8", "Lb0ELb1EEEvNSt11conditionalIXT8"
 
 
 def disassemble(lib):
@@ -47,15 +53,28 @@ def target(text, name):
 
 
 def loop_ranges(ins, name):
-    """The epoch loop as offset ranges: the largest backward-branch range, and
+    """The epoch loop as offset ranges: the largest backward-branch range (closed
+    by s_cbranch_*, or by s_branch where the compiler rotated the exit test to the
+    loop's head, as in the one-row flat Yuma 3 forms), and
     the out-of-line blocks behind it that the loop branches to and that branch
     back into it (the compiler parks rare blocks and, in the HS kernels, the
     refill blocks there)."""
-    best = (0, -1)
-    for off, text in ins:
-        t = target(text, name)
-        if t is not None and "s_cbranch" in text and t <= off and off - t > best[1] - best[0]:
-            best = (t, off)
+    def largest(kind):
+        r = (0, -1)
+        for off, text in ins:
+            t = target(text, name)
+            if t is not None and kind in text and "_exec" not in text and t <= off and off - t > r[1] - r[0]:
+                r = (t, off)
+        return r
+
+    # The largest range a conditional branch closes (not s_cbranch_exec*: those close loops over a wave's lanes,
+    # never one over epochs); but where a larger range closed by an unconditional branch
+    # lies apart from it, that one: the compiler rotated the epoch loop's exit test to its head, and the
+    # conditional range is a loop of the prologue. (Where the unconditional range holds the conditional one, its
+    # branch comes from an out-of-line block behind the loop, handled below.)
+    best, alt = largest("s_cbranch"), largest("s_branch")
+    if alt[1] - alt[0] > best[1] - best[0] and not (alt[0] <= best[0] and best[1] <= alt[1]):
+        best = alt
     ranges = [best]
     inside = lambda o: any(lo <= o <= hi for lo, hi in ranges)
     offs = [o for o, _ in ins]
@@ -80,14 +99,15 @@ def loop_ranges(ins, name):
 
 def waits(ins, name):
     ranges = loop_ranges(ins, name)
-    inside, outside, loads = collections.Counter(), collections.Counter(), 0
+    inside, outside, loads, words = collections.Counter(), collections.Counter(), 0, 0
     for off, text in ins:
         m = re.search(r"s_waitcnt.*?vmcnt\((\d+)\)", text)
         if m:
             (inside if any(lo <= off <= hi for lo, hi in ranges) else outside)[f"vmcnt({m.group(1)})"] += 1
         loads += "global_load_ubyte" in text
+        words += bool(re.search(r"global_load_dword\b", text))
     fmt = lambda c: " ".join(f"{k} x{v}" for k, v in sorted(c.items(), key=lambda kv: int(kv[0][6:-1]))) or "-"
-    return f"loop [{fmt(inside)}]  outside [{fmt(outside)}]  byte loads {loads}"
+    return f"loop [{fmt(inside)}]  outside [{fmt(outside)}]  byte loads {loads}  dword loads {words}"
 
 
 def main():
@@ -102,6 +122,16 @@ def main():
         s = re.search(r"k_bonds_elemILi(\d)ENS_9ElemShapeI(.*?)EEE(.*?)EEvN", name)
         print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
         for tag, k in (("RL   ", name), ("plain", twin)):
+            print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
+    print()
+    print("k_bonds_elem RW forms (validator-row events: both tables) and their RL twins")
+    for name in sorted(code):
+        if "k_bonds_elem" not in name or RW_TAIL not in name:
+            continue
+        twin = name.replace(RW_TAIL, RW_TWIN)
+        s = re.search(r"k_bonds_elemILi(\d)ENS_9ElemShapeI(.*?)EEE(.*?)EEvN", name)
+        print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
+        for tag, k in (("RW   ", name), ("RL   ", twin)):
             print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
 
 

@@ -3283,10 +3283,15 @@ struct BondArgsScMv : BondArgsSc {
 struct BondArgsRl : BondArgs {
   const unsigned char* rmask;  // [E][N][ceil(M / 8)]: bit c & 7 of byte c >> 3 set = column c is zeroed (k_reset_events)
 };
-template <bool SC, bool MV, bool RL = false>
-using ElemArgs = std::conditional_t<RL, BondArgsRl,
-                                    std::conditional_t<MV, std::conditional_t<SC, BondArgsScMv, BondArgsMv>,
-                                                       std::conditional_t<SC, BondArgsSc, BondArgs>>>;
+// ... and with validator-row events beside them (k_bonds_elem<.., RW = true, RL = false>): the second table
+struct BondArgsRw : BondArgsRl {
+  const unsigned* rowmask;  // [E][N][V] 32-bit words: non-zero = bond row v is zeroed (k_row_events)
+};
+template <bool SC, bool MV, bool RW = false, bool RL = false>
+using ElemArgs = std::conditional_t<RW, BondArgsRw,
+                                    std::conditional_t<RL, BondArgsRl,
+                                                       std::conditional_t<MV, std::conditional_t<SC, BondArgsScMv, BondArgsMv>,
+                                                                          std::conditional_t<SC, BondArgsSc, BondArgs>>>>;
 __host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
   return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
 }
@@ -4131,6 +4136,21 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // instantiation keeps its argument block and its code. Yuma 3 / Yuma 4 in
 // vector form with fp32 weights and an fp32 history or none, no schedule and
 // no movement: the four shapes plan_scan picks there.
+// RW: validator-row events beside them (yuma_run_events): a further form of
+// the same scan, the one with both tables. It stands before RL in the
+// parameter list and is instantiated as <.., RW = true, RL = false>, so that
+// the RL forms keep "RL = true" as their last template argument; inside the
+// kernel RL means "the column table is read", which RW implies.
+// k_row_events has resolved the chunk's row events into the table rowmask, one
+// 32-bit word per (epoch, scenario, validator), the index of rsd and sn: zero
+// keeps the row, a set word zeroes it. A lane owns R rows (row0 + G * i), so
+// it loads R words per epoch in flight, the row clamped as for rsd and sn,
+// at the head of fetch() beside the column byte and through per-lane pointers
+// in vector registers for the reasons given there; at the top of the epoch
+// row i's four values are ANDed with the complement of its word. A run with
+// row events always takes this form, on an all-zero column table where it has
+// no column events. The RW instantiations take BondArgsRw, BondArgsRl with the
+// second pointer appended.
 // SH: the block shape, an ElemShape (R, P, BS, CB as above; VECI: float4
 // incentive / bond_alpha loads; NT: non-temporal history stores; DPL: the
 // dividend-partial layout).
@@ -4140,8 +4160,10 @@ struct ElemShape {
   static constexpr bool VECI = VECI_, NT = NT_;
 };
 template <int VARIANT, typename SH, bool VEC, bool RQ = false, typename WT = float, bool HS = false,
-          typename HT = float, bool SC = false, bool MV = false, bool RL = false>
-__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RL> A) {
+          typename HT = float, bool SC = false, bool MV = false, bool RW = false, bool RL_ = false>
+__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, RL_> A) {
+  static_assert(!(RW && RL_), "row events: <.., RW = true, RL = false> is the scan with both tables");
+  constexpr bool RL = RL_ || RW;  // the column table is read
   constexpr int R = SH::R, P = SH::P, BS = SH::BS, CB = SH::CB, DPL = SH::DPL;
   constexpr bool VECI = SH::VECI, NT = SH::NT;
   static_assert(!MV || (VEC && DPL == DP_QTE && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<HT, float> && !HS),
@@ -4256,6 +4278,20 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RL> A
     rstep = N * rmb;
     asm("" : "+v"(rstep));  // (an empty statement: it only names the register class)
   }
+  // RW: the row-table word of each of the lane's R rows (the clamped row of rsd
+  // and sn: a row >= V reads row V - 1's word, and never reaches an output),
+  // walked like the column byte: one pointer per row and their common step in
+  // bytes, in vector registers
+  [[maybe_unused]] unsigned rwk[RW ? P : 1][RW ? R : 1];
+  [[maybe_unused]] const unsigned char* rwnext[RW ? R : 1];
+  [[maybe_unused]] int rwstep = 0;
+  if constexpr (RW) {
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+      rwnext[i] = reinterpret_cast<const unsigned char*>(A.rowmask + ((long long)A.t0 * N + n) * V + min(row0 + G * i, V - 1));
+    rwstep = N * V * 4;  // (a 32-bit byte step: check_native refuses row events at N * V >= 2^29)
+    asm("" : "+v"(rwstep));
+  }
   // DP_QTE: the quad partials of up to kQBuf epochs parked in LDS (one float
   // per wave row and epoch) and written out as contiguous runs when the
   // buffer fills or the launch ends: no global store inside the epoch loop
@@ -4292,6 +4328,14 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RL> A
     if constexpr (RL) {
       rmk[k] = *rnext;
       rnext += rstep;
+    }
+    // RW: and the R row words, for the same reason
+    if constexpr (RW) {
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        rwk[k][i] = *reinterpret_cast<const unsigned*>(rwnext[i]);
+        rwnext[i] += rwstep;
+      }
     }
 #pragma unroll
     for (int i = 0; i < R; ++i) {
@@ -4385,6 +4429,18 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RL> A
           asm("" : "+v"(keep));
 #pragma unroll
           for (int i = 0; i < R; ++i) B[i][cc] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, B[i][cc]) & keep);
+        }
+      }
+      if constexpr (RW) {
+        // The row events of this epoch: row i's keep mask is the complement of
+        // its table word (0, or all ones where an event fired), pinned to a
+        // vector register as above; it commutes with the column masks.
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+          unsigned keep = ~rwk[k][i];
+          asm("" : "+v"(keep));
+#pragma unroll
+          for (int cc = 0; cc < 4; ++cc) B[i][cc] = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, B[i][cc]) & keep);
         }
       }
       float bac[4], omba[4];
@@ -4693,6 +4749,26 @@ __global__ __launch_bounds__(256) void k_reset_events(const yuma_reset_event_t* 
       atomicOr(rmask + w, v);
     }
   }
+}
+
+// Validator-row events (yuma_run_events): the row events of the epochs
+// [t0, t1) resolved into the table rowmask (32-bit words [E][N][V], zeroed with
+// k_move_zero before the run's first chunk), one thread per event. An event
+// fires if a bond state exists (t >= 1, or B_init given: has_init); no
+// consensus rule applies to a validator. Every field is range-checked before
+// it addresses anything, and a non-zero reserved word makes the event void: a
+// bad event is ignored. A fired event sets every bit of its word with a
+// vector integer atomic OR, so duplicates and any order give the same table.
+__global__ __launch_bounds__(256) void k_row_events(const yuma_row_event_t* __restrict__ ev, int n_ev,
+                                                    unsigned* __restrict__ rowmask, int N, int E, int V, int t0,
+                                                    int t1, int has_init) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_ev) return;
+  const yuma_row_event_t e = ev[i];
+  const int t = e.epoch, n = e.scenario, v = e.row;
+  if (t < 0 || t >= E || t < t0 || t >= t1 || n < 0 || n >= N || v < 0 || v >= V || e.reserved != 0) return;
+  if (t == 0 && !has_init) return;
+  atomicOr(rowmask + ((long long)t * N + n) * V + v, 0xffffffffu);
 }
 
 // ---------------------------------------------------------------------------
@@ -6233,13 +6309,16 @@ struct ScanKey {
   bool full;     // W_b or the instantaneous bonds requested
   bool mv;       // the per-epoch bond movement (yuma_run_move; move_native holds)
   bool rl;       // reset events (yuma_run_resets; resets_native holds)
+  bool rw;       // validator-row events beside them (yuma_run_events; with rl)
 };
 // yuma_scan_plan_t as yuma_scan_plan reports it, and the movement choice
 // (the MV instantiation of the flat shape) beside it
 // and the reset-event choice (the RL instantiation of the shape)
+// and the row-event choice (the RW instantiation, the scan with both tables)
 struct ScanPlan : yuma_scan_plan_t {
   int mv;
   int rl;
+  int rw;
 };
 
 // The scan of a chunk: its kernel, that kernel's flags, the grid, and the
@@ -6273,6 +6352,7 @@ ScanPlan plan_scan(const ScanKey& k) {
   p.dpl = yk::DP_TV;
   p.mv = k.mv;  // (move_native: the key reaches the flat shapes below; launch_scan refuses any other)
   p.rl = k.rl;  // (resets_native: the key reaches the wide, tile-history and flat shapes; as above)
+  p.rw = k.rw;  // (the same set: yuma_events_native)
   // a kernel of `block` threads whose blocks own brows rows x bcols miners of `per` scenarios
   auto plan = [&](int form, int rows, int block, int brows, int bcols, bool rq, int per = 1) {
     p.form = form;
@@ -6338,7 +6418,7 @@ ScanPlan plan_scan(const ScanKey& k) {
 // instantiated where launch_scan is defined, and so keep their place in the
 // code object, behind the kernels of phase 1.)
 void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K,
-                 float* B_move = nullptr, const unsigned char* rmask = nullptr);
+                 float* B_move = nullptr, const unsigned char* rmask = nullptr, const unsigned* rowmask = nullptr);
 
 // The watched columns' scan over the chunk of A (k_bonds_watch), from the main
 // scan's own arguments: the same inputs, state and history countdown. Enqueued
@@ -6550,6 +6630,11 @@ size_t reset_table_bytes(int N, int E, int M) {
   return ((size_t)E * (size_t)N * (size_t)((M + 7) >> 3) + 255) & ~(size_t)255;
 }
 size_t reset_table_offset(size_t ws_bytes) { return (ws_bytes + 255) & ~(size_t)255; }
+// Bytes of the row table of a run with validator-row events (32-bit words
+// [E][N][V], padded to the same granule); it lies behind the reset table
+size_t row_table_bytes(int N, int E, int V) {
+  return ((size_t)E * (size_t)N * (size_t)V * 4 + 255) & ~(size_t)255;
+}
 
 // What run_plan and shard_stage_impl decide alike.
 int check_sizes(int variant, int N, int E, int V, int M) {
@@ -6693,6 +6778,11 @@ struct RunReq {
   int has_resets = 0;
   const yuma_reset_event_t* events = nullptr;
   int n_events = 0;
+  // yuma_run_events (has_rowev, which sets has_resets): the row events row_events[n_row_events] (device memory);
+  // n_row_events = 0 with a NULL list leaves has_rowev 0, the run yuma_run_resets makes
+  int has_rowev = 0;
+  const yuma_row_event_t* row_events = nullptr;
+  int n_row_events = 0;
 };
 
 // The history countdown (BondArgs::hnext) of the chunk from epoch A.t0 of the
@@ -6729,6 +6819,7 @@ ScanKey scan_key(const RunReq& q, bool vec, bool sched, bool run, bool strided) 
   k.full = q.out->Wb != nullptr || q.out->B_inst != nullptr;
   k.mv = q.has_move != 0;
   k.rl = q.has_resets != 0;
+  k.rw = q.has_rowev != 0;
   return k;
 }
 
@@ -6737,6 +6828,7 @@ ScanKey scan_key(const RunReq& q, bool vec, bool sched, bool run, bool strided) 
 struct RunPlan {
   Workspace ws, wk;
   size_t rmask_off;  // reset events: the table's offset in the workspace
+  size_t rowmask_off;  // row events: the row table's, behind it
   bool vec;
   int tiles;
   RowCfg rc;
@@ -6772,6 +6864,10 @@ int check_native(const RunReq& q, bool vec, bool sched, int K) {
       return fail(YUMA_EUNSUPPORTED,
                   "reset events (yuma_resets_native) need the vector form: W vector-aligned and the fp32 "
                   "matrices 16-byte aligned");
+    // (the scan steps through the row table by one epoch's N * V words, a 32-bit count of bytes)
+    if (q.has_rowev && (long long)N * V >= (1LL << 29))
+      return fail(YUMA_EUNSUPPORTED, "row events: N * V = %lld exceeds the row table's 32-bit epoch step (2^29 words)",
+                  (long long)N * V);
   }
   if (q.has_watch && !watch_native(variant, N, E, V, M, q.n_watch, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
     return fail(YUMA_EUNSUPPORTED,
@@ -6866,6 +6962,9 @@ int run_plan(const RunReq& q, RunPlan* p) {
   }
   if (q.n_events < 0) return fail(YUMA_EINVAL, "n_events=%d must not be negative", q.n_events);
   if (q.n_events > 0 && q.events == nullptr) return fail(YUMA_EINVAL, "n_events=%d with a NULL event list", q.n_events);
+  if (q.n_row_events < 0) return fail(YUMA_EINVAL, "n_row_events=%d must not be negative", q.n_row_events);
+  if (q.n_row_events > 0 && q.row_events == nullptr)
+    return fail(YUMA_EINVAL, "n_row_events=%d with a NULL row event list", q.n_row_events);
   const int full = out->Tv != nullptr;
   // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
   // params live in device memory, so the Python marshaller enforces it.
@@ -6873,7 +6972,10 @@ int run_plan(const RunReq& q, RunPlan* p) {
   p->wk = q.sched ? carve((char*)q.workspace + p->ws.bytes, variant, N, K, V, M, 0, true) : Workspace{};
   // (reset events: the table behind the carved workspace; they come without a schedule)
   p->rmask_off = q.has_resets ? reset_table_offset(p->ws.bytes) : 0;
-  const size_t need = q.has_resets ? p->rmask_off + reset_table_bytes(N, E, M) : p->ws.bytes + p->wk.bytes;
+  p->rowmask_off = q.has_rowev ? p->rmask_off + reset_table_bytes(N, E, M) : 0;
+  const size_t need = q.has_rowev      ? p->rowmask_off + row_table_bytes(N, E, V)
+                      : q.has_resets ? p->rmask_off + reset_table_bytes(N, E, M)
+                                     : p->ws.bytes + p->wk.bytes;
   if (need > q.ws_bytes)
     return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)", q.ws_bytes, need, full);
   p->tiles = (M + yk::kTileM - 1) / yk::kTileM;
@@ -7050,6 +7152,13 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     YK_LAUNCH(yk::k_move_zero, (nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024, 256, st,
               reinterpret_cast<float*>(rmask), nw);
   }
+  // row events: the row table likewise, each chunk's row events resolved beside the column events
+  unsigned* const rowmask = q.has_rowev ? reinterpret_cast<unsigned*>((char*)q.workspace + plan.rowmask_off) : nullptr;
+  if (q.has_rowev) {
+    const long long nw = (long long)(row_table_bytes(N, E, V) / 4);
+    YK_LAUNCH(yk::k_move_zero, (nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024, 256, st,
+              reinterpret_cast<float*>(rowmask), nw);
+  }
   for (int c0 = 0; c0 < E; c0 += chunk) {
     const int c1 = c0 + chunk < E ? c0 + chunk : E;
     const long long s0 = (long long)c0 * N;
@@ -7058,6 +7167,9 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     if (q.has_resets && q.n_events > 0)  // (counted under YUMA_PHASE_INCENTIVE, the phase it follows)
       YK_LAUNCH(yk::k_reset_events, ((long long)q.n_events + 255) / 256, 256, st, q.events, q.n_events, buf.C,
                 reinterpret_cast<unsigned*>(rmask), N, E, M, c0, c1, B_init != nullptr ? 1 : 0);
+    if (q.has_rowev && q.n_row_events > 0)
+      YK_LAUNCH(yk::k_row_events, ((long long)q.n_row_events + 255) / 256, 256, st, q.row_events, q.n_row_events,
+                rowmask, N, E, V, c0, c1, B_init != nullptr ? 1 : 0);
 
     // (A.W: the scan is launched for WT)
     yk::BondArgs A = bond_args(reinterpret_cast<const float*>(W), ws, buf, prm, B_init, Wprev_init, out, csb, N,
@@ -7075,7 +7187,7 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     if (q.has_rows)  // (likewise)
       launch_rows<WT>(st, variant, A, q.rows, q.n_rows, q.B_rows, sched, K);
     const ScanPlan scan = plan_scan(scan_key(q, vec, sched != nullptr, true, yk::hist_strided(A)));
-    launch_scan(st, scan, A, sched, K, q.B_move, rmask);
+    launch_scan(st, scan, A, sched, K, q.B_move, rmask, rowmask);
     const int ptiles = scan.ptiles;
     int dpl = scan.dpl;
     tm.mark(YUMA_PHASE_FINALIZE);
@@ -7268,7 +7380,7 @@ using Mode = std::integral_constant<int, MODE>;
 // other plan aborts (bad_plan).
 template <int VARIANT, bool VEC, typename WT, bool SC>
 void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move,
-                    const unsigned char* rmask) {
+                    const unsigned char* rmask, const unsigned* rowmask) {
   constexpr bool kPlain = std::is_same_v<WT, float> && !SC;  // fp32 W, no schedule
   constexpr bool kColnorm = VARIANT <= YUMA_VARIANT_YUMA2, kElem34 = VARIANT >= YUMA_VARIANT_YUMA3;
   const long long nb = p.grid;
@@ -7283,11 +7395,17 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
         constexpr bool kRq = decltype(RQ)::value;
         if ((p.rq != 0) != kRq || p.hist_bf16 || p.mv) bad_plan(p);
         with_flag<decltype(hs_mode)::value>(p, p.hs, [&](auto HS) {
-          yk::BondArgsRl As{};
+          // (RW: row events, the scan with both tables; BondArgsRw)
+          yk::BondArgsRw As{};
           static_cast<yk::BondArgs&>(As) = A;
           As.rmask = rmask;
-          YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, kRq, float, decltype(HS)::value, float, false, false, true>),
-                    nb, SH::BS, st, As);
+          As.rowmask = rowmask;
+          if (p.rw)
+            YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, kRq, float, decltype(HS)::value, float, false, false, true, false>),
+                      nb, SH::BS, st, As);
+          else
+            YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, kRq, float, decltype(HS)::value, float, false, false, false, true>),
+                      nb, SH::BS, st, static_cast<const yk::BondArgsRl&>(As));
         });
       };
       if (p.form == YUMA_SCAN_ELEM) switch (p.shape) {
@@ -7303,7 +7421,7 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
       bad_plan(p);
     }
   }
-  if (p.rl) bad_plan(p);
+  if (p.rl || p.rw) bad_plan(p);
   [[maybe_unused]] auto go = [&](auto kern) { YK_LAUNCH(kern, nb, p.block, st, A); };
   if constexpr (kColnorm && kPlain) {
     if (p.form == YUMA_SCAN_TILE && !p.rq)  // k_bonds, by RowCfg
@@ -7427,24 +7545,24 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
 // [A.t0, A.t1): the only place a bond scan is instantiated. uint16 weights
 // and input schedules are Yuma 3 / Yuma 4 in vector form (run_plan).
 void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move,
-                 const unsigned char* rmask) {
+                 const unsigned char* rmask, const unsigned* rowmask) {
   A.rowblocks = p.rowblocks;
   A.cblocks = p.cblocks;
   if ((p.rq && A.rq4 == nullptr) || (p.sc && sched == nullptr) || (p.mv != 0) != (B_move != nullptr) ||
-      (p.rl != 0) != (rmask != nullptr))
+      (p.rl != 0) != (rmask != nullptr) || (p.rw != 0) != (rowmask != nullptr) || (p.rw && !p.rl))
     bad_plan(p);
   with_variant(p.variant, [&](auto VARIANT) {
     constexpr int kVariant = decltype(VARIANT)::value;
     if constexpr (kVariant >= YUMA_VARIANT_YUMA3) {
       if (p.vector_form && p.w_u16)
         return with_bool(p.sc != 0, [&](auto SC) {
-          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K, B_move, rmask);
+          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K, B_move, rmask, rowmask);
         });
-      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K, B_move, rmask);
+      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K, B_move, rmask, rowmask);
     }
     if (p.w_u16 || p.sc) bad_plan(p);
     with_bool(p.vector_form != 0, [&](auto VEC) {
-      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K, B_move, rmask);
+      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K, B_move, rmask, rowmask);
     });
   });
 }
@@ -7519,6 +7637,18 @@ void read_resets(const yuma_reset_event_t* events_dev, int n_events, RunReq* q) 
   q->has_resets = (n_events != 0 || events_dev != nullptr) ? 1 : 0;
   q->events = events_dev;
   q->n_events = n_events;
+}
+
+// yuma_run_events / yuma_graph_create_events: the row event list as given beside the column list (run_plan refuses
+// what is wrong with either); n_row_events = 0 with a NULL list is "no row events", the run of yuma_run_resets. A
+// run with row events takes the scan with both tables, on an all-zero column table where it has no column events.
+void read_events(const yuma_reset_event_t* events_dev, int n_events, const yuma_row_event_t* row_events_dev,
+                 int n_row_events, RunReq* q) {
+  read_resets(events_dev, n_events, q);
+  q->has_rowev = (n_row_events != 0 || row_events_dev != nullptr) ? 1 : 0;
+  if (q->has_rowev) q->has_resets = 1;
+  q->row_events = row_events_dev;
+  q->n_row_events = n_row_events;
 }
 
 // A direct run: validate, then enqueue on the caller's stream, in the weight type the request names.
@@ -7679,6 +7809,29 @@ int yuma_run_resets(int variant, const yuma_params_t* params_dev, int N, int E, 
 }
 
 int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  return resets_native(variant, N, E, V, M, out, flags) ? 1 : 0;
+}
+
+size_t yuma_workspace_bytes_events(int variant, int N, int E, int V, int M, int full_outputs) {
+  if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
+  return yuma_workspace_bytes_resets(variant, N, E, V, M, full_outputs) + row_table_bytes(N, E, V);
+}
+
+int yuma_run_events(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
+                    const float* W, const float* S, const float* B_init, const float* Wprev_init,
+                    const yuma_outputs_t* out, const yuma_reset_event_t* events_dev, int n_events,
+                    const yuma_row_event_t* row_events_dev, int n_row_events,
+                    void* workspace, size_t workspace_bytes, int chunk_epochs,
+                    const yuma_run_options_t* opts, void* stream, float* phase_ms) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_events(events_dev, n_events, row_events_dev, n_row_events, &q);
+  return run_direct(q);
+}
+
+// (the native set of row events is that of the column events: the same scan shapes)
+int yuma_events_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
   return resets_native(variant, N, E, V, M, out, flags) ? 1 : 0;
 }
 
@@ -7845,6 +7998,19 @@ int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params
            chunk_epochs, nullptr, nullptr};
   if (const int err = read_opts(opts, &q)) return err;
   read_resets(events_dev, n_events, &q);
+  return graph_create_impl(graph, q);
+}
+
+int yuma_graph_create_events(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                             int E, int V, int M, const float* W, const float* S,
+                             const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                             const yuma_reset_event_t* events_dev, int n_events,
+                             const yuma_row_event_t* row_events_dev, int n_row_events, void* workspace,
+                             size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_events(events_dev, n_events, row_events_dev, n_row_events, &q);
   return graph_create_impl(graph, q);
 }
 

@@ -64,6 +64,10 @@ EXPORTED_SYMBOLS = (
     "yuma_run_resets",
     "yuma_resets_native",
     "yuma_graph_create_resets",
+    "yuma_workspace_bytes_events",
+    "yuma_run_events",
+    "yuma_events_native",
+    "yuma_graph_create_events",
     "yuma_scan_plan",
     "yuma_epoch",
     "yuma_synth_weights",
@@ -157,6 +161,15 @@ class YumaResetEventC(ctypes.Structure):
 
 
 assert ctypes.sizeof(YumaResetEventC) == 16, ctypes.sizeof(YumaResetEventC)
+
+
+class YumaRowEventC(ctypes.Structure):
+    """yuma_row_event_t (include/yuma_hip.h): 16 bytes."""
+    _fields_ = [("epoch", ctypes.c_int32), ("scenario", ctypes.c_int32), ("row", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(YumaRowEventC) == 16, ctypes.sizeof(YumaRowEventC)
 
 
 class YumaRunOptionsC(ctypes.Structure):
@@ -282,6 +295,18 @@ def load_library(path: str | None = None):
             lib.yuma_workspace_bytes_resets.restype = sz
             lib.yuma_resets_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
             lib.yuma_resets_native.restype = i32
+        # validator-row events: yuma_run_resets's arguments, the second list and its length after n_events
+        if hasattr(lib, "yuma_run_events"):  # (A/B libraries of older sources lack them)
+            a = lib.yuma_run_resets.argtypes
+            lib.yuma_run_events.argtypes = a[:13] + [vp, i32] + a[13:]
+            lib.yuma_run_events.restype = i32
+            a = lib.yuma_graph_create_resets.argtypes
+            lib.yuma_graph_create_events.argtypes = a[:14] + [vp, i32] + a[14:]
+            lib.yuma_graph_create_events.restype = i32
+            lib.yuma_workspace_bytes_events.argtypes = [i32, i32, i32, i32, i32, i32]
+            lib.yuma_workspace_bytes_events.restype = sz
+            lib.yuma_events_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
+            lib.yuma_events_native.restype = i32
         if hasattr(lib, "yuma_scan_plan"):  # (A/B libraries of older sources lack it)
             lib.yuma_scan_plan.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp]
             lib.yuma_scan_plan.restype = i32
@@ -662,6 +687,53 @@ def resets_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool 
     return bool(load_library().yuma_resets_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
 
 
+def events_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False,
+                  want: tuple[str, ...] = (), *, shared_inputs: bool = False, w_u16: bool = False,
+                  hist_bf16: bool = False) -> bool:
+    """Whether `run(..., row_resets=)` with these arguments applies the row
+    events inside its bond scan (yuma_events_native; needs the library, not a
+    GPU): the set of resets_native. Otherwise `run` cuts the run at the event
+    epochs and RunGraph refuses."""
+    names = {"Dn", "C", "I", "B_final", *want}
+    if want_hist:
+        names.add("B_hist")
+    outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
+    flags = ((RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+             | (RUN_HIST_BF16 if hist_bf16 else 0))
+    return bool(load_library().yuma_events_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
+
+
+def workspace_bytes_events(variant: int, N: int, E: int, V: int, M: int, full_outputs: bool = False) -> int:
+    """yuma_workspace_bytes_events: the workspace of a run with row events (the
+    reset-event workspace and the row table, one 32-bit word per epoch,
+    scenario and validator)."""
+    return int(load_library().yuma_workspace_bytes_events(variant, N, E, V, M, 1 if full_outputs else 0))
+
+
+def _row_resets_host(row_resets, N: int, E: int, V: int) -> torch.Tensor:
+    """A host row-event list as a CPU int64 tensor [n, 4] of (epoch, scenario,
+    validator, 0), validated: integers, shape [n, 3] or [n, 4], epoch in
+    [0, E), scenario in [0, N), validator in [0, V), the fourth (reserved)
+    field 0. ValueError otherwise."""
+    t = row_resets if isinstance(row_resets, torch.Tensor) else torch.as_tensor(np.asarray(row_resets))
+    if t.numel() == 0:
+        return torch.zeros((0, 4), dtype=torch.int64)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"row_resets must hold integers, not {t.dtype}")
+    if t.dim() != 2 or t.shape[1] not in (3, 4):
+        raise ValueError(f"row_resets must be (epoch, scenario, validator) events, shape [n, 3] or [n, 4], "
+                         f"not {tuple(t.shape)}")
+    h = t.detach().to(device="cpu", dtype=torch.int64)
+    if h.shape[1] == 3:
+        h = torch.cat([h, torch.zeros((h.shape[0], 1), dtype=torch.int64)], dim=1)
+    for j, (name, lo, hi) in enumerate((("epoch", 0, E), ("scenario", 0, N), ("validator", 0, V), ("reserved", 0, 1))):
+        bad = (h[:, j] < lo) | (h[:, j] >= hi)
+        if bool(bad.any()):
+            k = int(bad.nonzero()[0])
+            raise ValueError(f"row_resets[{k}]: {name} {int(h[k, j])} is outside [{lo}, {hi})")
+    return h
+
+
 def _resets_host(resets, N: int, E: int, M: int) -> torch.Tensor:
     """A host event list as a CPU int64 tensor [n, 4] of (epoch, scenario,
     column, mode), validated: integers, epoch in [0, E), scenario in [0, N),
@@ -688,7 +760,7 @@ def _resets_host(resets, N: int, E: int, M: int) -> torch.Tensor:
 
 
 def _run_segments(variant, params, W, S, B_init, Wprev_init, ev, *, N, E, M, h_epochs, want_hist, want,
-                  chunk_epochs, workspace, out, shared_inputs, hist_stride) -> "RunResult":
+                  chunk_epochs, workspace, out, shared_inputs, hist_stride, row_ev=None) -> "RunResult":
     """run(..., resets=) where the events are not native: the chain that defines
     them. The run is cut at the distinct event epochs; each segment runs on the
     existing path from the carried B_final, whose columns torch zeroes between
@@ -696,7 +768,10 @@ def _run_segments(variant, params, W, S, B_init, Wprev_init, ev, *, N, E, M, h_e
     params' own reset is folded into the event list and cleared in copied
     records; the history's phase is carried from segment to segment; per-epoch
     outputs and history slots are concatenated. ev: CPU int64 [n, 4]; events
-    the device code would ignore are dropped here."""
+    the device code would ignore are dropped here. row_ev: the row events
+    (run(..., row_resets=)), CPU int64 [n, 4] of (epoch, scenario, validator,
+    reserved) or None: the run is cut at their epochs too and the rows are
+    zeroed beside the columns."""
     dev = device()
     ok = ((ev[:, 0] >= 0) & (ev[:, 0] < E) & (ev[:, 1] >= 0) & (ev[:, 1] < N) & (ev[:, 2] >= -1) & (ev[:, 2] < M)
           & ((ev[:, 3] == RESET_ALWAYS) | ((ev[:, 3] == RESET_IF_ZERO_CONSENSUS) & (ev[:, 2] >= 0) & (ev[:, 0] >= 1))))
@@ -715,10 +790,22 @@ def _run_segments(variant, params, W, S, B_init, Wprev_init, ev, *, N, E, M, h_e
     by_epoch: dict = {}
     for t, n, c, mode in events:
         by_epoch.setdefault(t, []).append((n, c, mode))
+    rows_by_epoch: dict = {}
+    if row_ev is not None:
+        V_ = W.shape[2]
+        for t, n, v, z in row_ev.tolist():
+            if 0 <= t < E and 0 <= n < N and 0 <= v < V_ and z == 0:
+                rows_by_epoch.setdefault(t, []).append((n, v))
+                by_epoch.setdefault(t, [])
     cuts = [0] + sorted(t for t in by_epoch if t > 0) + [E]
 
-    def apply(B, evs, prevC):
-        """B [N, V, M] with the columns of the events evs zeroed (prevC [N, M]: C of the epoch before)."""
+    def apply(B, evs, prevC, rows=()):
+        """B [N, V, M] with the columns of the events evs and the rows (n, v) zeroed (prevC [N, M]: C of the epoch
+        before)."""
+        if rows:
+            B = B.clone()
+            for n, v in rows:
+                B[n, v, :] = 0.0
         mask = torch.zeros((N, M), dtype=torch.bool, device=dev)
         for n, c, mode in evs:
             if mode == RESET_ALWAYS:
@@ -732,12 +819,12 @@ def _run_segments(variant, params, W, S, B_init, Wprev_init, ev, *, N, E, M, h_e
 
     B = None if B_init is None else _as_dev(B_init, dev)
     if B is not None and 0 in by_epoch:
-        B = apply(B, by_epoch[0], None)
+        B = apply(B, by_epoch[0], None, rows_by_epoch.get(0, ()))
     parts, hist, last = [], [], None
     names = ("Dn", "C", "I") + tuple(want)
     for a, b in zip(cuts[:-1], cuts[1:]):
         if a > 0:
-            B = apply(last.B_final, by_epoch[a], last.C[-1])
+            B = apply(last.B_final, by_epoch[a], last.C[-1], rows_by_epoch.get(a, ()))
         stored = [t for t in h_epochs if a <= t < b] if want_hist else []
         last = run(variant, prm, W[a:b], S[a:b], B, Wprev_init if a == 0 else None, want_hist=bool(stored), want=want,
                    chunk_epochs=chunk_epochs, workspace=workspace, shared_inputs=shared_inputs,
@@ -755,6 +842,8 @@ def _run_segments(variant, params, W, S, B_init, Wprev_init, ev, *, N, E, M, h_e
             res[k] = t.copy_(res[k])
     extra = {k: res[k] for k in want}
     extra.update(resets_path="segments", resets=None, w_path=last.extra["w_path"], hist_path="f32")
+    if row_ev is not None:
+        extra["row_resets"] = None
     return RunResult(res["Dn"], res["C"], res["I"], res["B_final"], res.get("B_hist"), extra,
                      h_epochs if want_hist else None)
 
@@ -1080,7 +1169,7 @@ _OUT_SHAPES = {
 
 
 def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None, move=None,
-            resets=None, rows=None) -> None:
+            resets=None, rows=None, row_events=None) -> None:
     """The run's one launch: yuma_run_opts, yuma_run_sched under a native
     schedule, or yuma_run_watch with a native watch list (watch: the int32
     device list, B_watch and the buffer whose address the engine gets); with `capture`, their yuma_graph_create_* twins,
@@ -1089,12 +1178,20 @@ def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watc
     absent: NULL, 0, NULL). resets: the int32 device event list [n, 4], for
     yuma_run_resets (no schedule, watch list or B_move beside it). rows: the
     int32 device row list, B_rows and the buffer whose address the engine gets,
-    for yuma_run_rows (its watch list and B_move may both be absent)."""
+    for yuma_run_rows (its watch list and B_move may both be absent).
+    row_events: the int32 device row-event list [n, 4], for yuma_run_events
+    (yuma_run_resets's arguments, the second list after the first, which may be
+    absent: NULL, 0)."""
     if rows is not None:  # yuma_run_move's arguments (B_move may be NULL), the row list after B_move
         run_fn, graph_fn = lib.yuma_run_rows, lib.yuma_graph_create_rows
         w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
         args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
                 + w + (_ptr(move),) + (rows[0].data_ptr(), rows[0].numel(), rows[2].data_ptr()) + tail[7:])
+    elif row_events is not None:  # yuma_run_resets's arguments, the row list and its length after n_events
+        run_fn, graph_fn = lib.yuma_run_events, lib.yuma_graph_create_events
+        n_ev, n_row = (0 if resets is None else resets.shape[0]), row_events.shape[0]
+        args = (head + tail[:7] + (resets.data_ptr() if n_ev else None, n_ev)
+                + (row_events.data_ptr() if n_row else None, n_row) + tail[7:])
     elif resets is not None:  # yuma_run_opts's arguments, the list and its length after `out`
         run_fn, graph_fn = lib.yuma_run_resets, lib.yuma_graph_create_resets
         n_ev = resets.shape[0]
@@ -1134,7 +1231,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
         hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None,
-        watch=None, want_move: bool = False, resets=None, watch_rows=None) -> RunResult:
+        watch=None, want_move: bool = False, resets=None, watch_rows=None, row_resets=None) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -1234,7 +1331,28 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     (Yuma 0 / 1 / 2, shared inputs, single_call) the run writes an fp32
     history, the rows are gathered from it on the device and the history is
     dropped unless asked for (extra["rows_path"] == "dense"; a captured run
-    raises EngineError instead)."""
+    raises EngineError instead).
+    row_resets: validator-row events, a sequence of (epoch, scenario,
+    validator) tuples or an int32 tensor [n, 3] or [n, 4] (the fourth field is
+    reserved: 0): before epoch t's update of scenario n the event zeroes bond
+    row v, B[n, v, :] = 0, if a bond state exists (t >= 1, or B_init given);
+    no consensus rule applies to a validator. Duplicates and any order are
+    allowed; resets= and the params' own reset keep working beside the row
+    events, and the two kinds commute. A host sequence (or CPU tensor) is
+    validated before anything touches a GPU (ValueError); a CUDA tensor is
+    passed through unchecked, and the device code ignores an event out of
+    range or with a non-zero reserved field. Every output has the bits of the
+    chain of runs cut at the event epochs and resumed from B_final with the
+    rows and columns zeroed. It combines with resets=, want_hist, hist_stride /
+    hist_first, B_init and chunk_epochs; like resets= it takes Yuma 3 / Yuma 4
+    only, and not sched, watch, watch_rows, want_move, single_call or a
+    bfloat16 history (ValueError). Where events_native holds (and the buffers
+    have the vector form's alignment) the bond scan applies the events itself
+    (yuma_run_events, extra["resets_path"] == "native"; extra["row_resets"] is
+    the int32 device list [n, 4] a captured run re-reads at every replay -- a
+    caller's own contiguous int32 [n, 4] device tensor is used as it is);
+    elsewhere that chain runs (extra["resets_path"] == "segments"; a captured
+    run raises EngineError instead)."""
     h_bf16 = hist_dtype == torch.bfloat16
     # the row list, validated before anything touches a GPU
     rows_host = None if watch_rows is None else _watch_host(watch_rows, W.shape[2], "watch_rows", "validator", "V")
@@ -1252,6 +1370,22 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                 raise ValueError(f"a device event list must be int32 [n, 4], not {resets.dtype} {tuple(resets.shape)}")
         else:
             resets_host = _resets_host(resets, len(params) if shared_inputs else W.shape[1], W.shape[0], W.shape[3])
+    rowev_host = None
+    if row_resets is not None:  # likewise
+        if variant not in (VARIANT_YUMA3, VARIANT_YUMA4):
+            raise ValueError("row_resets= takes Yuma 3 / Yuma 4 only")
+        for name, given in (("sched", sched is not None), ("watch_rows", watch_rows is not None),
+                            ("watch", watch is not None), ("want_move", bool(want_move)),
+                            ("single_call", bool(single_call)), ("hist_dtype=torch.bfloat16", h_bf16)):
+            if given:
+                raise ValueError(f"row_resets= does not combine with {name}")
+        if isinstance(row_resets, torch.Tensor) and row_resets.is_cuda:
+            if row_resets.dtype != torch.int32 or row_resets.dim() != 2 or row_resets.shape[1] not in (3, 4):
+                raise ValueError(f"a device row-event list must be int32 [n, 3] or [n, 4], not {row_resets.dtype} "
+                                 f"{tuple(row_resets.shape)}")
+        else:
+            rowev_host = _row_resets_host(row_resets, len(params) if shared_inputs else W.shape[1], W.shape[0],
+                                          W.shape[2])
     dev, N, E, K, sched_host, h_epochs, watch_host = _check_args(
         params, W, S, B_init, Wprev_init, out, single_call=single_call, shared_inputs=shared_inputs,
         hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched, watch=watch,
@@ -1306,15 +1440,26 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                               "resets_native(variant, N, E, V, M, ...) and vector-aligned buffers")
         if phase_ms is not None:
             raise ValueError("phase_ms times one launch: the events of this call are not native")
-        ev = resets_host if resets_host is not None else resets.detach().to(device="cpu", dtype=torch.int64)
+        if resets is None:
+            ev = torch.zeros((0, 4), dtype=torch.int64)
+        else:
+            ev = resets_host if resets_host is not None else resets.detach().to(device="cpu", dtype=torch.int64)
+        row_ev = None
+        if row_resets is not None:
+            row_ev = rowev_host if rowev_host is not None else row_resets.detach().to(device="cpu", dtype=torch.int64)
+            if row_ev.shape[1] == 3:
+                row_ev = torch.cat([row_ev, torch.zeros((row_ev.shape[0], 1), dtype=torch.int64)], dim=1)
         return _run_segments(variant, params, W_arg, S_arg, B_init, Wprev_init, ev, N=N, E=E, M=M, h_epochs=h_epochs,
                              want_hist=want_hist or (out or {}).get("B_hist") is not None, want=want,
                              chunk_epochs=chunk_epochs, workspace=workspace, out=out, shared_inputs=shared_inputs,
-                             hist_stride=hist_stride)
+                             hist_stride=hist_stride, row_ev=row_ev)
 
     out_names = tuple(want) + tuple(k for k, v in (out or {}).items() if v is not None and k != "B_hist")
     if resets is not None and not resets_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs,
                                                 w_u16=W.dtype == torch.uint16):
+        return segments()
+    if row_resets is not None and not events_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs,
+                                                    w_u16=W.dtype == torch.uint16):
         return segments()
     if want_move and (want_hist or (out or {}).get("B_hist") is not None
                       or not move_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs)):
@@ -1396,6 +1541,16 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     if want_move and not _vector_form(W, w_u16, B_init, Wprev_init, o, False):  # (nothing is launched yet)
         return move_dense()
     resets_dev = None
+    rowev_dev = None
+    if row_resets is not None:
+        if not _vector_form(W, False, B_init, Wprev_init, o, False):  # (nothing is launched yet)
+            return segments()
+        if rowev_host is not None:
+            rowev_dev = rowev_host.to(device=dev, dtype=torch.int32)
+        elif row_resets.shape[1] == 3:  # 16-byte records: the reserved word added on the device
+            rowev_dev = torch.nn.functional.pad(row_resets, (0, 1)).contiguous()
+        else:
+            rowev_dev = row_resets if row_resets.is_contiguous() else row_resets.contiguous()  # unchecked
     if resets is not None:
         if not _vector_form(W, False, B_init, Wprev_init, o, False):  # (nothing is launched yet)
             return segments()
@@ -1427,6 +1582,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     full = o.get("Tv") is not None
     if sched_dev is not None:
         nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
+    elif rowev_dev is not None and rowev_dev.shape[0] > 0:
+        nbytes = int(lib.yuma_workspace_bytes_events(variant, N, E, V, M, 1 if full else 0))
     elif resets_dev is not None and resets_dev.shape[0] > 0:
         nbytes = int(lib.yuma_workspace_bytes_resets(variant, N, E, V, M, 1 if full else 0))
     else:
@@ -1448,7 +1605,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         _launch(lib, dev, (variant, prm.data_ptr(), N, E), K, sched_dev,
                 (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
                  workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
-                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move, resets=resets_dev, rows=rows_arg)
+                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move, resets=resets_dev, rows=rows_arg,
+                row_events=rowev_dev)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -1462,6 +1620,9 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     if resets is not None:  # how the events were applied: by the bond scan, or by cutting the run
         keep["resets_path"] = "native"
         keep["resets"] = resets_dev
+    if row_resets is not None:
+        keep["resets_path"] = "native"
+        keep["row_resets"] = rowev_dev
     hist = o.get("B_hist")
     if h_bf16 and hist is not None and not hist_native:  # the fp32 history, rounded to nearest even
         hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)

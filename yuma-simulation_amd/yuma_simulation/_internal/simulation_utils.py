@@ -94,7 +94,7 @@ def _reward_key(config: YumaConfig) -> tuple:
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                     want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None,
                     dedup_inputs: bool = False, bonds_columns=None, bonds_movement: bool = False,
-                    bond_resets=None, bonds_validators=None):
+                    bond_resets=None, bonds_validators=None, validator_resets=None):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
@@ -149,7 +149,20 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     validators a study follows over every miner. The engine then keeps no
     [V, M] history (engine.run's watch_rows). Combines with bonds_every,
     dedup_inputs, bonds_movement and bonds_dtype as bonds_columns does; not
-    with bonds_columns (one list, one shape) nor bond_resets (ValueError)."""
+    with bonds_columns (one list, one shape) nor bond_resets (ValueError).
+    validator_resets: None, or one entry per run: None or a list of (epoch,
+    validator) pairs: the run's bond row of that validator is zeroed before
+    epoch `epoch`, unconditionally -- a validator that leaves or whose hotkey
+    is replaced (engine.run's row_resets: one engine call per group still, the
+    scenario index added). Any number of pairs, in any order, beside
+    bond_resets and the case's own reset. Epochs and indices are plain ints,
+    the index in [0, V) (ValueError otherwise, before anything touches a GPU);
+    an epoch outside [0, E) is never reached. The reference has no rule for a
+    validator's row, so a non-empty entry for a run whose version is not Yuma
+    3.x / Yuma 4 is a ValueError, never silently ignored. Combines with
+    bond_resets and bonds_every; not with dedup_inputs, bonds_columns,
+    bonds_validators, bonds_movement or bonds_dtype=torch.bfloat16
+    (ValueError)."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
     if bonds_dtype not in (None, torch.float32, torch.bfloat16):
@@ -180,6 +193,13 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                             ("bonds_movement", bonds_movement), ("bonds_dtype=torch.bfloat16", bonds_dtype == torch.bfloat16)):
             if given:
                 raise ValueError(f"bond_resets does not combine with {name}")
+    if validator_resets is not None:  # validated on the host, before anything touches a GPU
+        validator_resets = _check_validator_resets(runs, validator_resets)
+        for name, given in (("dedup_inputs", dedup_inputs), ("bonds_columns", bonds_columns is not None),
+                            ("bonds_validators", bonds_validators is not None), ("bonds_movement", bonds_movement),
+                            ("bonds_dtype=torch.bfloat16", bonds_dtype == torch.bfloat16)):
+            if given:
+                raise ValueError(f"validator_resets does not combine with {name}")
     # the result lists are thousands of fresh containers (the sheet: 1512
     # dividend lists): the cyclic collector would sweep the process's whole
     # heap several times while they are built; they hold no cycles
@@ -187,7 +207,40 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
         return _run_simulations(runs, want_bonds, want_incentives, bonds_every=operator.index(bonds_every),
                                 bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs),
                                 bonds_columns=bonds_columns, bonds_movement=bool(bonds_movement),
-                                bond_resets=bond_resets, bonds_validators=bonds_validators)
+                                bond_resets=bond_resets, bonds_validators=bonds_validators,
+                                **({"validator_resets": validator_resets} if validator_resets is not None else {}))
+
+
+def _check_validator_resets(runs, validator_resets) -> list:
+    """run_simulations' validator_resets as one list of (epoch, validator) int
+    pairs per run (empty: none), epochs outside the run dropped. ValueError for
+    anything but plain ints, a negative epoch, an index outside [0, V), or a
+    non-empty entry for a run whose version is not Yuma 3.x / Yuma 4."""
+    if (isinstance(validator_resets, (str, bytes)) or not hasattr(validator_resets, "__len__")
+            or len(validator_resets) != len(runs)):
+        raise ValueError(f"validator_resets must hold one entry (None or a list of (epoch, validator) pairs) per run: "
+                         f"{len(runs)} runs")
+    out = []
+    for k, (r, pairs) in enumerate(zip(runs, validator_resets)):
+        kept = []
+        if pairs is not None and len(pairs) > 0:
+            if resolve_version(r.yuma_version)[0] not in (engine.VARIANT_YUMA3, engine.VARIANT_YUMA4):
+                raise ValueError(f"validator_resets[{k}]: run {k} ('{r.case.name}', {r.yuma_version}) is not Yuma 3.x / "
+                                 f"Yuma 4: there is no rule for a validator's row there")
+            E, V, _ = r.case.packed_inputs()[0].shape
+            for pair in pairs:
+                if not isinstance(pair, (tuple, list)) or len(pair) != 2 or not all(type(x) is int for x in pair):
+                    raise ValueError(f"validator_resets[{k}]: {pair!r} is not an (epoch, validator) pair of ints")
+                epoch, index = pair
+                if epoch < 0:
+                    raise ValueError(f"validator_resets[{k}]: epoch {epoch} is negative")
+                if not 0 <= index < V:
+                    raise ValueError(f"validator_resets[{k}]: index {index} is outside [0, V={V}) of run {k} "
+                                     f"('{r.case.name}', {r.yuma_version})")
+                if epoch < E:
+                    kept.append((epoch, index))
+        out.append(kept)
+    return out
 
 
 def _check_bond_resets(runs, bond_resets) -> list:
@@ -272,7 +325,8 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
                      totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False,
-                     bonds_columns=None, bonds_movement: bool = False, bond_resets=None, bonds_validators=None):
+                     bonds_columns=None, bonds_movement: bool = False, bond_resets=None, bonds_validators=None,
+                     validator_resets=None):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -318,6 +372,9 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
         # the group's reset events: each run's pairs under its version's rule, with its scenario index
         events = [(e, j, i, packed[k][1]) for j, k in enumerate(idx) if packed[k][1] != engine.RESET_NONE
                   for e, i in (bond_resets[k] if bond_resets is not None else ())]
+        # ... and its validator-row events
+        row_events = [(e, j, v) for j, k in enumerate(idx)
+                      for e, v in (validator_resets[k] if validator_resets is not None else ())]
         watch = bonds_columns if want_bonds else None  # the watched columns in place of the [V, M] history
         rows = bonds_validators if want_bonds else None  # ... or the watched validator rows
         dense = want_bonds and watch is None and rows is None
@@ -325,7 +382,8 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
             variant, params, W, S, want_hist=dense, hist_stride=bonds_every, sched=sched,
             hist_dtype=bonds_dtype if dense else None, watch=watch,
             **({"watch_rows": rows} if rows is not None else {}),
-            **({"want_move": True} if bonds_movement else {}), **({"resets": events} if events else {}))))
+            **({"want_move": True} if bonds_movement else {}), **({"resets": events} if events else {}),
+            **({"row_resets": row_events} if row_events else {}))))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
         hist = None
