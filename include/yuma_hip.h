@@ -477,6 +477,77 @@ int yuma_run_rows(int variant, const yuma_params_t* params_dev, int N, int E, in
 int yuma_rows_native(int variant, int N, int E, int V, int M, int n_rows, int flags);
 
 /* ------------------------------------------------------------------------
+ * Per-validator bond summary per epoch: which validator's bonds still move,
+ * how large is each validator's position, when did each one settle.
+ *
+ * yuma_run_rowstat writes B_rowstat [E][N][V][3] (fp32, device memory) beside
+ * the run's other outputs. B_t is the bond state after epoch t, exactly the
+ * bits the dense fp32 history holds; B_{-1} is B_init, or zeros without one.
+ *   B_rowstat[t][n][v][0] = max over m of |B_t[n][v][m] - B_{t-1}[n][v][m]|
+ *   B_rowstat[t][n][v][1] = max over m of |B_t[n][v][m]|
+ *   B_rowstat[t][n][v][2] = sum over m of B_t[n][v][m]
+ * [0] and [1] are yuma_run_move's two maxima taken over one row: one fp32
+ * subtraction per element, a reset at t counts as movement, NaN as in
+ * torch.amax, -0 counts as +0; bit-equal to (hist[t] - hist[t-1]).abs()
+ * .amax(-1) and hist[t].abs().amax(-1) on the dense history, and their
+ * maximum over v is B_move[t][n] bit for bit.
+ * [2] is summed in the canonical order of the dividend partials with every
+ * incentive replaced by 1. Per 64-miner tile: each lane adds its four
+ * consecutive columns in order starting from +0, and the tile's 16 lanes are
+ * joined by the xor-butterfly tree (lane distances 1, 2, 4, 8). Tiles p_k are
+ * joined into quads Q_b = (p_4b + p_4b+1) + (p_4b+2 + p_4b+3), absent tiles
+ * counting 0; S_g is the sequential sum of the quads b = g (mod 4), and the
+ * total is ((S_0 + S_1) + S_2) + S_3 -- the order that gives D. The bits are
+ * the same on both native scan shapes and for every chunk_epochs.
+ * Every other output, B_final included, keeps the bits of the same run
+ * without B_rowstat.
+ *
+ * The history-less scan forms all three at the update: the maxima go out as
+ * unsigned max atomics, one per row, statistic, epoch and 256-miner column
+ * block, into B_rowstat, which the engine zeroes itself with a small kernel
+ * on the run's stream (inside a captured graph too: every replay starts from
+ * zero); the totals go through a second array of quad partials in the
+ * workspace (yuma_workspace_bytes_rowstat >= yuma_workspace_bytes) and a twin
+ * of the dividends' summing kernel.
+ *
+ * The arguments are yuma_run_rows's with B_rowstat after B_rows. The row list
+ * is optional here: n_rows == 0 with NULL rows_dev and NULL B_rows means "no
+ * row list" (here only), and the watch list likewise as in yuma_run_move.
+ * Watch and row lists are kernels of their own and combine. A schedule
+ * pointer or a B_move does not: YUMA_EUNSUPPORTED.
+ *
+ * Native (yuma_rowstat_native returns 1; host only, makes no HIP call; of
+ * `out` it reads only which pointers are non-NULL; `flags` are the run's
+ * flags): Yuma 3 and Yuma 4 (scalar or liquid alpha, any reset of the
+ * parameter record), the vector form (M % 4 == 0; W and the fp32 matrices
+ * 16-byte aligned), any V up to YUMA_MAX_VALIDATORS, no
+ * YUMA_RUN_SHARED_INPUTS, YUMA_RUN_W_U16 or YUMA_RUN_HIST_BF16, out->B_hist
+ * NULL, none of Wn / Wc / Wb / B_inst / Tv requested -- the calls whose scan
+ * is YUMA_ELEM_FLAT1 / YUMA_ELEM_FLAT2 on fp32 weights. Elsewhere the entry
+ * points return YUMA_EUNSUPPORTED before the first launch and the caller
+ * reduces an fp32 history itself. yuma_scan_plan_t has no room for a further
+ * field at its fixed size, so yuma_scan_plan reports the shape of such a run
+ * (FLAT1 / FLAT2) and not the summary form.
+ *
+ * Refusals, in this order, all before the first launch and without a HIP call
+ * (yuma_graph_create_rowstat: the same code and yuma_last_error text, before
+ * the capture opens): as yuma_run_rows up to the row list's (which apply only
+ * when a row list is given); a NULL B_rowstat (YUMA_EINVAL); the workspace
+ * size (yuma_workspace_bytes_rowstat); the schedule, watch list, movement and
+ * row list refusals of yuma_run_rows; a schedule pointer, a B_move or reset
+ * events beside the summary; the summary not native; then not in vector form
+ * (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and YUMA_RUN_W_U16 as ever.
+ * ---------------------------------------------------------------------- */
+size_t yuma_workspace_bytes_rowstat(int variant, int N, int E, int V, int M, int full_outputs);
+int yuma_run_rowstat(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                     const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                     const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
+                     int n_watch, float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows,
+                     float* B_rows, float* B_rowstat, void* workspace, size_t workspace_bytes,
+                     int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms);
+int yuma_rowstat_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
+
+/* ------------------------------------------------------------------------
  * Bond reset events: any number of column resets inside one run.
  *
  * A subnet deregisters miners all the time, and every deregistration clears
@@ -729,6 +800,14 @@ int yuma_graph_create_rows(yuma_graph_t* graph, int variant, const yuma_params_t
                            float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows,
                            float* B_rows, void* workspace, size_t workspace_bytes, int chunk_epochs,
                            const yuma_run_options_t* opts);
+/* yuma_graph_create_rows with the row summary (yuma_run_rowstat's arguments). */
+int yuma_graph_create_rowstat(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
+                              int E, int K, int V, int M, const float* W, const float* S,
+                              const int32_t* sched_dev, const float* B_init, const float* Wprev_init,
+                              const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                              float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows,
+                              float* B_rows, float* B_rowstat, void* workspace, size_t workspace_bytes,
+                              int chunk_epochs, const yuma_run_options_t* opts);
 /* yuma_graph_create_opts with reset events (yuma_run_resets's arguments). */
 int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
                              int E, int V, int M, const float* W, const float* S,

@@ -55,6 +55,10 @@ def kernels(lib, every=False):
 
 
 def key(name):
+    # <..., RW, RL> takes conditional_t<SH::RS, BondArgsRs, ElemArgs<SC, MV, RW, RL>>: the name of before the row
+    # summary (an ElemShapeRs shape, BondArgsRs: only in a library that has it)
+    name = re.sub(r"EEEvNSt11conditionalIXsrT0_2RSENS_10BondArgsRsENS\d+_(IXT8_ENS_10BondArgsRwE.*)E4typeE$",
+                  r"EEEvNSt11conditional\1", name)
     # <..., SC, MV, RW = false, RL> takes ElemArgs<SC, MV, RW, RL>: the name of before the validator-row events (RW =
     # true, BondArgsRw: only in a library that has them)
     name = re.sub(r"Lb0E(Lb[01])EEEvNSt11conditionalIXT8_ENS_10BondArgsRwENS3_IXT9_ENS_10BondArgsRlE(.*)E4typeE$",

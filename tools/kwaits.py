@@ -133,6 +133,17 @@ def main():
         print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
         for tag, k in (("RW   ", name), ("RL   ", twin)):
             print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
+    print()
+    print("k_bonds_elem RS forms (the per-validator bond summary: an ElemShapeRs shape) and their plain twins")
+    for name in sorted(code):
+        if "k_bonds_elem" not in name or "ElemShapeRsI" not in name:
+            continue
+        twin = name.replace("ENS_11ElemShapeRsI", "ENS_9ElemShapeI")
+        s = re.search(r"k_bonds_elemILi(\d)ENS_11ElemShapeRsI(.*?)EEE(.*?)EEvN", name)
+        print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
+        for tag, k in (("RS   ", name), ("plain", twin)):
+            if k in code:
+                print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
 
 
 if __name__ == "__main__":

@@ -3292,6 +3292,11 @@ using ElemArgs = std::conditional_t<RW, BondArgsRw,
                                     std::conditional_t<RL, BondArgsRl,
                                                        std::conditional_t<MV, std::conditional_t<SC, BondArgsScMv, BondArgsMv>,
                                                                           std::conditional_t<SC, BondArgsSc, BondArgs>>>>;
+// ... with the per-validator bond summary (k_bonds_elem<.., RS = true>)
+struct BondArgsRs : BondArgs {
+  float* B_rowstat;  // [E][N][V][3], zeroed before the run's first scan (k_move_zero)
+  float* tpart;      // the I = 1 twin of dpart (DP_QTE), from the workspace
+};
 __host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
   return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
 }
@@ -4151,6 +4156,27 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // row events always takes this form, on an all-zero column table where it has
 // no column events. The RW instantiations take BondArgsRw, BondArgsRl with the
 // second pointer appended.
+// RS (SH::RS, the shape an ElemShapeRs): the per-validator bond summary
+// (yuma_run_rowstat), B_rowstat[t][n][v][3].
+// [0] and [1] are MV's two maxima taken over the row v alone: the same bit
+// masks and unsigned maxima, one pair per row of the lane. In the flat shapes
+// a wave holds one row of its 256-miner column block (LPR = 64), so uwmax64
+// reduces over exactly the lanes that share the row. The wave parks the pair
+// of each of its R rows in LDS (mbuf) and sends them from behind the unrolled
+// epoch bodies as MV does: one returnless unsigned max atomic per row,
+// statistic, epoch and column block, to B_rowstat, which the engine has zeroed
+// (k_move_zero). [2] is the row total Σ_m B_t[v][m] in the canonical order of
+// the dividend partials with every incentive replaced by 1: beside d the lane
+// sums its four columns in the same order, the 64-miner tile and the quad
+// Q_b = (p0 + p1) + (p2 + p3) are joined by the same exchanges, the quad
+// partial is parked beside qbuf's (tbuf) and goes to tpart in dpart's DP_QTE
+// layout; k_rowstat_sum, the twin of k_dte_sum, joins the quads as D's are
+// joined (S_g sequential over b = g mod 4, then ((S_0 + S_1) + S_2) + S_3) and
+// stores the total. So the bits depend neither on the flat shape nor on the
+// chunking. Yuma 3 / Yuma 4 in vector form, fp32 weights, screened
+// reciprocals, no history, schedule, movement or events. The RS
+// instantiations take BondArgsRs, BondArgs with the two pointers appended;
+// every other instantiation keeps its argument block and its code.
 // SH: the block shape, an ElemShape (R, P, BS, CB as above; VECI: float4
 // incentive / bond_alpha loads; NT: non-temporal history stores; DPL: the
 // dividend-partial layout).
@@ -4158,14 +4184,27 @@ template <int R_, int P_, bool VECI_, bool NT_, int BS_, int CB_, int DPL_>
 struct ElemShape {
   static constexpr int R = R_, P = P_, BS = BS_, CB = CB_, DPL = DPL_;
   static constexpr bool VECI = VECI_, NT = NT_;
+  static constexpr bool RS = false;
+};
+// The same shape with the row summary (RS above). The flag rides on the shape's
+// type, not on k_bonds_elem's parameter list, so that the names of the other
+// forms keep their tail: the last two template arguments stay RW and RL.
+template <int R_, int P_, bool VECI_, bool NT_, int BS_, int CB_, int DPL_>
+struct ElemShapeRs : ElemShape<R_, P_, VECI_, NT_, BS_, CB_, DPL_> {
+  static constexpr bool RS = true;
 };
 template <int VARIANT, typename SH, bool VEC, bool RQ = false, typename WT = float, bool HS = false,
           typename HT = float, bool SC = false, bool MV = false, bool RW = false, bool RL_ = false>
-__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, RL_> A) {
+__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SH::RS, BondArgsRs, ElemArgs<SC, MV, RW, RL_>> A) {
   static_assert(!(RW && RL_), "row events: <.., RW = true, RL = false> is the scan with both tables");
   constexpr bool RL = RL_ || RW;  // the column table is read
+  constexpr bool RS = SH::RS;     // the row summary: a property of the shape's type (ElemShapeRs)
   constexpr int R = SH::R, P = SH::P, BS = SH::BS, CB = SH::CB, DPL = SH::DPL;
   constexpr bool VECI = SH::VECI, NT = SH::NT;
+  static_assert(!RS || (VEC && RQ && DPL == DP_QTE && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float> &&
+                        std::is_same_v<HT, float> && !HS && !SC && !MV && !RL),
+                "row summary: Yuma 3 / Yuma 4, vector form, fp32 weights, the history-less flat shapes alone");
+  constexpr bool OLD = MV || RS;  // the row's old values are kept past the update
   static_assert(!MV || (VEC && DPL == DP_QTE && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<HT, float> && !HS),
                 "bond movement: Yuma 3 / Yuma 4, vector form, the history-less flat shapes");
   static_assert(!SC || (VEC && VARIANT >= YUMA_VARIANT_YUMA3), "input schedules: Yuma 3 / Yuma 4, vector form");
@@ -4301,8 +4340,11 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
   __shared__ float qbuf[DPL == DP_QTE ? NWB * R * kQBuf : 1];
   int tq = A.t0;  // first epoch held in qbuf
   // MV: each wave's two maxima of up to kQBuf epochs, parked and sent like the quad partials
-  __shared__ unsigned mbuf[MV ? NWB * 2 * kQBuf : 1];
+  // (RS: the two maxima of each of the wave's R rows)
+  __shared__ unsigned mbuf[MV ? NWB * 2 * kQBuf : RS ? NWB * R * 2 * kQBuf : 1];
   [[maybe_unused]] int tm = A.t0;  // first epoch held in mbuf
+  // RS: the I = 1 quad partials, parked and written out with qbuf's
+  __shared__ float tbuf[RS ? NWB * R * kQBuf : 1];
   // a duplicate scenario of a rank class reads its representative's column sums
   // (the rank pass skips duplicate slices; k_incentive copies R, not csb / csr)
   const int ncs = (COLNORM && A.csrep != nullptr) ? A.csrep[n] : n;
@@ -4396,13 +4438,14 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
       [[maybe_unused]] bool rfire = false;
       [[maybe_unused]] int rcol = 0;
       [[maybe_unused]] unsigned mvd = 0u, mvb = 0u;  // MV: this lane's max |B_t - B_{t-1}| and max |B_t|, as bits
+      [[maybe_unused]] unsigned rsd_[RS ? R : 1], rsb_[RS ? R : 1];  // RS: the same two per row of the lane
       if (!COLNORM && has_old && reset_mode != YUMA_RESET_NONE && t == reset_epoch &&
           (reset_all || (reset_index >= 0 && reset_index < M))) {
         bool fire = reset_mode == YUMA_RESET_ALWAYS;
         if (reset_mode == YUMA_RESET_IF_ZERO_CONSENSUS && t >= 1 && !reset_all) fire = zero_c;
         const int c = reset_index - m;
         if (fire && (reset_all || (c >= 0 && c < 4))) {
-          if constexpr (MV) {
+          if constexpr (OLD) {
             rfire = true;
             rcol = c;
           } else {
@@ -4477,7 +4520,7 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
         auto mn = [](float a, float b) { return SHORT ? vmin(a, b) : tmin(a, b); };
         auto mx = [](float a, float b) { return SHORT ? vmax(a, b) : tmax(a, b); };
         [[maybe_unused]] float old[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if constexpr (MV) {
+        if constexpr (OLD) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
             old[c] = B[i][c];
@@ -4580,6 +4623,18 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
             mvb = max(mvb, in ? a : 0u);
           }
         }
+        if constexpr (RS) {
+          // as MV, kept per row (a select, never a lane's branch)
+          const bool in = row < V && m < M;
+          unsigned rd_ = 0u, rb_ = 0u;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            rd_ = max(rd_, __builtin_bit_cast(unsigned, B[i][c] - old[c]) & 0x7fffffffu);
+            rb_ = max(rb_, __builtin_bit_cast(unsigned, B[i][c]) & 0x7fffffffu);
+          }
+          rsd_[i] = in ? rd_ : 0u;
+          rsb_[i] = in ? rb_ : 0u;
+        }
         if ((HS ? hst : A.B_hist != nullptr) && row < V) {
           if constexpr (std::is_same_v<HT, float>) {
             float* hp = A.B_hist + (HS ? hsl : slice) * VM + (long long)row * M;
@@ -4600,19 +4655,26 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
           }
         }
         float d = 0.0f;
+        [[maybe_unused]] float s1 = 0.0f;  // RS: d with every incentive 1
         // M % 4 == 0: a column quad is wholly in or out. (Not with the
         // history stream: there the lane branch cost the c2 scan 1.65 ->
         // 2.71 ms, same box.)
         if (VEC && !NT) {
-          if (m < M)
+          if (m < M) {
 #pragma unroll
             for (int c = 0; c < 4; ++c) d = d + B[i][c] * ri[k][c];
+            if constexpr (RS) {
+#pragma unroll
+              for (int c = 0; c < 4; ++c) s1 = s1 + B[i][c];
+            }
+          }
         } else {
 #pragma unroll
           for (int c = 0; c < 4; ++c)
             if (m + c < M) d = d + B[i][c] * ri[k][c];
         }
         d = wsum16(d);  // sum_row16's xor-butterfly tree, on DPP
+        if constexpr (RS) s1 = wsum16(s1);
         if constexpr (DPL == DP_QTE || DPL == DP_VQ) {
           // the wave holds one quad of this row (CB >= 256, LPR >= 64):
           // Q = (p0 + p1) + (p2 + p3) in every lane (xor butterflies pair
@@ -4624,6 +4686,13 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
           if constexpr (DPL == DP_QTE) {
             float* qb = qbuf + ((threadIdx.x >> 6) * R + i) * kQBuf;
             if (lane == 0) qb[t - tq] = q;
+            [[maybe_unused]] float* tb_ = tbuf;
+            if constexpr (RS) {
+              float q1 = s1 + __shfl_xor(s1, 16, 64);
+              q1 = q1 + __shfl_xor(q1, 32, 64);
+              tb_ = tbuf + ((threadIdx.x >> 6) * R + i) * kQBuf;
+              if (lane == 0) tb_[t - tq] = q1;
+            }
             if (t - tq == kQBuf - 1 || t == A.t1 - 1) {  // wave-uniform
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
               __builtin_amdgcn_wave_barrier();
@@ -4631,6 +4700,11 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
               float* dq = A.dpart + ((long long)(n * nq + quad) * V + row) * A.ep + tq;
               if (row < V && quad < nq)
                 for (int e = lane; e <= t - tq; e += 64) dq[e] = qb[e];
+              if constexpr (RS) {
+                float* dt = A.tpart + ((long long)(n * nq + quad) * V + row) * A.ep + tq;
+                if (row < V && quad < nq)
+                  for (int e = lane; e <= t - tq; e += 64) dt[e] = tb_[e];
+              }
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
               __builtin_amdgcn_wave_barrier();
               __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -4656,6 +4730,18 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
           mb[kQBuf + t - tm] = wb;
         }
       }
+      if constexpr (RS) {
+        // each row's two maxima over the wave, parked like MV's pair
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+          const unsigned wd = uwmax64(rsd_[i]), wb = uwmax64(rsb_[i]);
+          unsigned* mb = mbuf + ((threadIdx.x >> 6) * R + i) * 2 * kQBuf;
+          if (lane == 0) {
+            mb[t - tm] = wd;
+            mb[kQBuf + t - tm] = wb;
+          }
+        }
+      }
       if (HS && hst) {
         hnext += A.hstride;
         hsl += N;
@@ -4665,6 +4751,35 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<SC, MV, RW, R
       if (t + P < A.t1) {
         fetch(k, t + P, snext);
         if constexpr (SC) snext = sched_at(t + P + 1);
+      }
+    }
+    if constexpr (RS) {
+      // RS: as MV below, for each of the wave's R rows: one returnless atomic per
+      // row, statistic and epoch from this column block (a row >= V sends none;
+      // wave-uniform, a wave holds one row per pass)
+      static_assert(kQBuf % P == 0, "the parking buffer fills at the end of a pass over the P bodies");
+      static_assert(LPR == 64, "a wave holds one row of its column block");
+      const int td = min(tb + P, A.t1);  // epochs [tm, td) are parked; wave-uniform
+      if (td - tm == kQBuf || td == A.t1) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+          const int row = row0 + G * i;
+          const unsigned* mb = mbuf + ((threadIdx.x >> 6) * R + i) * 2 * kQBuf;
+          unsigned* rp = reinterpret_cast<unsigned*>(A.B_rowstat) + (((long long)tm * N + n) * V + min(row, V - 1)) * 3;
+          if (row < V)
+            for (int e = lane; e < td - tm; e += 64) {
+              (void)__hip_atomic_fetch_max(rp + (long long)e * N * V * 3, mb[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              (void)__hip_atomic_fetch_max(rp + (long long)e * N * V * 3 + 1, mb[kQBuf + e], __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        tm = td;
       }
     }
     if constexpr (MV) {
@@ -5817,6 +5932,39 @@ __global__ __launch_bounds__(256) void k_dte_sum(const float* __restrict__ dpart
   }
 }
 
+// The row totals of the per-validator bond summary (yuma_run_rowstat): the
+// I = 1 quad partials tpart (DP_QTE) -> B_rowstat[t][n][v][2] for the epochs
+// [t0, t1), k_dte_sum's twin: the same grid, loads and order of additions,
+// stored at stride 3. (A twin, so that k_dte_sum keeps its code.)
+__global__ __launch_bounds__(256) void k_rowstat_sum(const float* __restrict__ tpart, int N, int V, int tiles,
+                                                     int ep, int t0, int t1, float* __restrict__ B_rowstat) {
+  __shared__ float part[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nq = dp_quads(tiles);
+  const int vgroups = (V + 3) / 4;
+  const int tgroups = (t1 - (t0 & ~15) + 15) / 16;
+  const int vg = blockIdx.x % vgroups;
+  const int tg = (blockIdx.x / vgroups) % tgroups;
+  const int n = blockIdx.x / (vgroups * tgroups);
+  const int t = (t0 & ~15) + tg * 16 + (lane & 15);
+  const int v = vg * 4 + (lane >> 4);
+  const bool ok = t >= t0 && t < t1 && v < V;
+  const float* p = tpart + ((long long)n * nq * V + (ok ? v : 0)) * ep + (ok ? t : 0);
+  const long long bstride = (long long)V * ep;
+  float acc = 0.0f;
+#pragma unroll 8
+  for (int b = wave; b < nq; b += 4) acc = acc + p[b * bstride];
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && ok) {
+    float d = part[0][lane];
+    d = d + part[1][lane];
+    d = d + part[2][lane];
+    d = d + part[3][lane];
+    B_rowstat[(((long long)t * N + n) * V + v) * 3 + 2] = d;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Miner-column shards: the per-shard partial sums a
 // caller reduces across shards between stages, and the hand-back of the
@@ -6294,6 +6442,9 @@ template <bool VEC>
 using ElemFlat1 = yk::ElemShape<1, 4, VEC, false, 256, 256, yk::DP_QTE>;
 template <bool VEC>
 using ElemFlat2 = yk::ElemShape<2, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE>;
+// ... and with the row summary (vector form only)
+using ElemFlat1Rs = yk::ElemShapeRs<1, 4, true, false, 256, 256, yk::DP_QTE>;
+using ElemFlat2Rs = yk::ElemShapeRs<2, kNoHistP2, true, false, 256, 256, yk::DP_QTE>;
 
 // What the choice of a scan depends on.
 struct ScanKey {
@@ -6310,15 +6461,18 @@ struct ScanKey {
   bool mv;       // the per-epoch bond movement (yuma_run_move; move_native holds)
   bool rl;       // reset events (yuma_run_resets; resets_native holds)
   bool rw;       // validator-row events beside them (yuma_run_events; with rl)
+  bool rs;       // the per-validator bond summary (yuma_run_rowstat; rowstat_native holds)
 };
 // yuma_scan_plan_t as yuma_scan_plan reports it, and the movement choice
 // (the MV instantiation of the flat shape) beside it
 // and the reset-event choice (the RL instantiation of the shape)
 // and the row-event choice (the RW instantiation, the scan with both tables)
+// and the row-summary choice (the RS instantiation of the flat shape)
 struct ScanPlan : yuma_scan_plan_t {
   int mv;
   int rl;
   int rw;
+  int rs;
 };
 
 // The scan of a chunk: its kernel, that kernel's flags, the grid, and the
@@ -6353,6 +6507,7 @@ ScanPlan plan_scan(const ScanKey& k) {
   p.mv = k.mv;  // (move_native: the key reaches the flat shapes below; launch_scan refuses any other)
   p.rl = k.rl;  // (resets_native: the key reaches the wide, tile-history and flat shapes; as above)
   p.rw = k.rw;  // (the same set: yuma_events_native)
+  p.rs = k.rs;  // (rowstat_native: the key reaches the flat shapes below; as above)
   // a kernel of `block` threads whose blocks own brows rows x bcols miners of `per` scenarios
   auto plan = [&](int form, int rows, int block, int brows, int bcols, bool rq, int per = 1) {
     p.form = form;
@@ -6418,7 +6573,8 @@ ScanPlan plan_scan(const ScanKey& k) {
 // instantiated where launch_scan is defined, and so keep their place in the
 // code object, behind the kernels of phase 1.)
 void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K,
-                 float* B_move = nullptr, const unsigned char* rmask = nullptr, const unsigned* rowmask = nullptr);
+                 float* B_move = nullptr, const unsigned char* rmask = nullptr, const unsigned* rowmask = nullptr,
+                 float* B_rowstat = nullptr, float* tpart = nullptr);
 
 // The watched columns' scan over the chunk of A (k_bonds_watch), from the main
 // scan's own arguments: the same inputs, state and history countdown. Enqueued
@@ -6623,6 +6779,27 @@ bool resets_native(int variant, int N, int E, int V, int M, const yuma_outputs_t
   return true;
 }
 
+// Whether a run with these arguments forms the per-validator bond summary
+// inside its scan (yuma_rowstat_native): the calls plan_scan sends to the flat
+// history-less shapes with fp32 weights -- the element-wise variants in vector
+// form, any validator count, per-scenario inputs, no history and none of the
+// per-epoch matrices requested. Only those shapes are instantiated with RS.
+bool rowstat_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  if (variant != YUMA_VARIANT_YUMA3 && variant != YUMA_VARIANT_YUMA4) return false;
+  if (N < 1 || E < 1 || V < 1 || M < 1 || V > YUMA_MAX_VALIDATORS || (M % 4) != 0) return false;
+  if (flags & (YUMA_RUN_SHARED_INPUTS | YUMA_RUN_W_U16 | YUMA_RUN_HIST_BF16)) return false;
+  if (out != nullptr && (out->B_hist || out->Wn || out->Wc || out->Wb || out->B_inst || out->Tv)) return false;
+  return true;
+}
+
+// Bytes of the I = 1 quad partials of a run with the row summary (dpart's
+// DP_QTE extent, padded to the workspace's 256-byte granule); they lie behind
+// the carved workspace (reset_table_offset: such a run has no reset table)
+size_t rowstat_part_bytes(int N, int E, int V, int M) {
+  const size_t tiles = (size_t)(M + yk::kTileM - 1) / yk::kTileM;
+  return ((size_t)N * yk::dp_quads((int)tiles) * V * (size_t)dte_stride(E) * 4 + 255) & ~(size_t)255;
+}
+
 // Bytes of the reset table of a run (bytes [E][N][ceil(M / 8)], padded to the
 // 256-byte granule the workspace is carved in; k_reset_events addresses it as
 // 32-bit words) and its offset behind the carved workspace of ws_bytes bytes
@@ -6783,6 +6960,10 @@ struct RunReq {
   int has_rowev = 0;
   const yuma_row_event_t* row_events = nullptr;
   int n_row_events = 0;
+  // yuma_run_rowstat (has_rowstat): the per-validator bond summary B_rowstat [E][N][V][3]; its watch and row
+  // lists may be empty (has_watch / has_rows stay 0)
+  int has_rowstat = 0;
+  float* B_rowstat = nullptr;
 };
 
 // The history countdown (BondArgs::hnext) of the chunk from epoch A.t0 of the
@@ -6820,6 +7001,7 @@ ScanKey scan_key(const RunReq& q, bool vec, bool sched, bool run, bool strided) 
   k.mv = q.has_move != 0;
   k.rl = q.has_resets != 0;
   k.rw = q.has_rowev != 0;
+  k.rs = q.has_rowstat != 0;
   return k;
 }
 
@@ -6829,6 +7011,7 @@ struct RunPlan {
   Workspace ws, wk;
   size_t rmask_off;  // reset events: the table's offset in the workspace
   size_t rowmask_off;  // row events: the row table's, behind it
+  size_t tpart_off;  // row summary: the I = 1 quad partials' offset in the workspace
   bool vec;
   int tiles;
   RowCfg rc;
@@ -6891,6 +7074,23 @@ int check_native(const RunReq& q, bool vec, bool sched, int K) {
                 "a row list is not native for variant=%d V=%d shared=%d (yuma_rows_native): run the fp32 "
                 "history and gather the rows",
                 variant, V, wsh);
+  if (q.has_rowstat) {
+    // what the RS forms are not instantiated with, then the predicate, then the alignment
+    if (sched || q.has_move || q.has_resets)
+      return fail(YUMA_EUNSUPPORTED,
+                  "the row summary does not combine with an input schedule, B_move or reset events: run the fp32 "
+                  "history and reduce it");
+    const int f = (wsh ? YUMA_RUN_SHARED_INPUTS : 0) | (q.w_u16 ? YUMA_RUN_W_U16 : 0) | (q.hist_bf16 ? YUMA_RUN_HIST_BF16 : 0);
+    if (!rowstat_native(variant, N, E, V, M, out, f))
+      return fail(YUMA_EUNSUPPORTED,
+                  "the row summary is not native for variant=%d V=%d M=%d flags=0x%x or the requested outputs "
+                  "(yuma_rowstat_native): run the fp32 history and reduce it",
+                  variant, V, M, f);
+    if (!vec)
+      return fail(YUMA_EUNSUPPORTED,
+                  "the row summary (yuma_rowstat_native) needs the vector form: W vector-aligned and the fp32 "
+                  "matrices 16-byte aligned");
+  }
   if (q.hist_bf16) {
     if (out->B_hist == nullptr) return fail(YUMA_EINVAL, "YUMA_RUN_HIST_BF16 without out->B_hist");
     if (!hist_bf16_native(variant, N, E, V, M, out, wsh ? YUMA_RUN_SHARED_INPUTS : 0))
@@ -6960,6 +7160,7 @@ int run_plan(const RunReq& q, RunPlan* p) {
     if (rows_bpr(M, 1) * q.n_rows * N > INT_MAX)
       return fail(YUMA_EINVAL, "n_rows=%d: N n_rows M elements exceed the row kernel's grid", q.n_rows);
   }
+  if (q.has_rowstat && q.B_rowstat == nullptr) return fail(YUMA_EINVAL, "B_rowstat is NULL");
   if (q.n_events < 0) return fail(YUMA_EINVAL, "n_events=%d must not be negative", q.n_events);
   if (q.n_events > 0 && q.events == nullptr) return fail(YUMA_EINVAL, "n_events=%d with a NULL event list", q.n_events);
   if (q.n_row_events < 0) return fail(YUMA_EINVAL, "n_row_events=%d must not be negative", q.n_row_events);
@@ -6973,8 +7174,12 @@ int run_plan(const RunReq& q, RunPlan* p) {
   // (reset events: the table behind the carved workspace; they come without a schedule)
   p->rmask_off = q.has_resets ? reset_table_offset(p->ws.bytes) : 0;
   p->rowmask_off = q.has_rowev ? p->rmask_off + reset_table_bytes(N, E, M) : 0;
+  // (row summary: the I = 1 partials behind the carved workspace and a schedule's staging set; check_native
+  // refuses it beside a schedule or events)
+  p->tpart_off = q.has_rowstat ? reset_table_offset(p->ws.bytes + p->wk.bytes) : 0;
   const size_t need = q.has_rowev      ? p->rowmask_off + row_table_bytes(N, E, V)
                       : q.has_resets ? p->rmask_off + reset_table_bytes(N, E, M)
+                      : q.has_rowstat ? p->tpart_off + rowstat_part_bytes(N, E, V, M)
                                      : p->ws.bytes + p->wk.bytes;
   if (need > q.ws_bytes)
     return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)", q.ws_bytes, need, full);
@@ -7159,6 +7364,12 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     YK_LAUNCH(yk::k_move_zero, (nw + 255) / 256 < 1024 ? (nw + 255) / 256 : 1024, 256, st,
               reinterpret_cast<float*>(rowmask), nw);
   }
+  // row summary: B_rowstat zeroed likewise (the scan's max atomics start from it; the totals are stored)
+  float* const tpart = q.has_rowstat ? reinterpret_cast<float*>((char*)q.workspace + plan.tpart_off) : nullptr;
+  if (q.has_rowstat) {
+    const long long nr = (long long)E * N * V * 3;
+    YK_LAUNCH(yk::k_move_zero, (nr + 255) / 256 < 1024 ? (nr + 255) / 256 : 1024, 256, st, q.B_rowstat, nr);
+  }
   for (int c0 = 0; c0 < E; c0 += chunk) {
     const int c1 = c0 + chunk < E ? c0 + chunk : E;
     const long long s0 = (long long)c0 * N;
@@ -7187,7 +7398,7 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     if (q.has_rows)  // (likewise)
       launch_rows<WT>(st, variant, A, q.rows, q.n_rows, q.B_rows, sched, K);
     const ScanPlan scan = plan_scan(scan_key(q, vec, sched != nullptr, true, yk::hist_strided(A)));
-    launch_scan(st, scan, A, sched, K, q.B_move, rmask, rowmask);
+    launch_scan(st, scan, A, sched, K, q.B_move, rmask, rowmask, q.B_rowstat, tpart);
     const int ptiles = scan.ptiles;
     int dpl = scan.dpl;
     tm.mark(YUMA_PHASE_FINALIZE);
@@ -7197,6 +7408,9 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
                 ws.dpart, N, V, ptiles, A.ep, c0, c1, ws.dsum);
       dsrc = ws.dsum;
       dpl = yk::DP_PRE;
+      if (q.has_rowstat)  // the row totals of the chunk, joined as D is (a row-summary scan is DP_QTE: launch_scan)
+        YK_LAUNCH(yk::k_rowstat_sum, (long long)N * ((c1 - (c0 & ~15) + 15) / 16) * ((V + 3) / 4), 256, st, tpart, N,
+                  V, ptiles, A.ep, c0, c1, q.B_rowstat);
     }
     launch_finalize(st, ns, dsrc, ws, variant, V, s0, ptiles, ws.tvc, ws.tvn, out, dpl, tiles);
     if (out->Sn != nullptr)
@@ -7380,7 +7594,7 @@ using Mode = std::integral_constant<int, MODE>;
 // other plan aborts (bad_plan).
 template <int VARIANT, bool VEC, typename WT, bool SC>
 void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move,
-                    const unsigned char* rmask, const unsigned* rowmask) {
+                    const unsigned char* rmask, const unsigned* rowmask, float* B_rowstat, float* tpart) {
   constexpr bool kPlain = std::is_same_v<WT, float> && !SC;  // fp32 W, no schedule
   constexpr bool kColnorm = VARIANT <= YUMA_VARIANT_YUMA2, kElem34 = VARIANT >= YUMA_VARIANT_YUMA3;
   const long long nb = p.grid;
@@ -7421,7 +7635,29 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
       bad_plan(p);
     }
   }
-  if (p.rl || p.rw) bad_plan(p);
+  if constexpr (kElem34 && VEC && kPlain) {
+    // the row summary (RS; BondArgsRs): the two flat shapes with the screened
+    // reciprocal plan_scan picks there, no history, movement or events
+    if (p.rs) {
+      auto elem_rs = [&](auto sh) {
+        using SH = decltype(sh);
+        if (!p.rq || p.hist || p.hs || p.hist_bf16 || p.mv || p.rl || p.rw) bad_plan(p);
+        yk::BondArgsRs As{};
+        static_cast<yk::BondArgs&>(As) = A;
+        As.B_rowstat = B_rowstat;
+        As.tpart = tpart;
+        YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, true>), nb, SH::BS, st, As);
+      };
+      if (p.form == YUMA_SCAN_ELEM) switch (p.shape) {
+          case YUMA_ELEM_FLAT1:
+            return elem_rs(ElemFlat1Rs{});
+          case YUMA_ELEM_FLAT2:
+            return elem_rs(ElemFlat2Rs{});
+        }
+      bad_plan(p);
+    }
+  }
+  if (p.rl || p.rw || p.rs) bad_plan(p);
   [[maybe_unused]] auto go = [&](auto kern) { YK_LAUNCH(kern, nb, p.block, st, A); };
   if constexpr (kColnorm && kPlain) {
     if (p.form == YUMA_SCAN_TILE && !p.rq)  // k_bonds, by RowCfg
@@ -7545,24 +7781,25 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
 // [A.t0, A.t1): the only place a bond scan is instantiated. uint16 weights
 // and input schedules are Yuma 3 / Yuma 4 in vector form (run_plan).
 void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32_t* sched, int K, float* B_move,
-                 const unsigned char* rmask, const unsigned* rowmask) {
+                 const unsigned char* rmask, const unsigned* rowmask, float* B_rowstat, float* tpart) {
   A.rowblocks = p.rowblocks;
   A.cblocks = p.cblocks;
   if ((p.rq && A.rq4 == nullptr) || (p.sc && sched == nullptr) || (p.mv != 0) != (B_move != nullptr) ||
-      (p.rl != 0) != (rmask != nullptr) || (p.rw != 0) != (rowmask != nullptr) || (p.rw && !p.rl))
+      (p.rl != 0) != (rmask != nullptr) || (p.rw != 0) != (rowmask != nullptr) || (p.rw && !p.rl) ||
+      (p.rs != 0) != (B_rowstat != nullptr) || (p.rs != 0) != (tpart != nullptr))
     bad_plan(p);
   with_variant(p.variant, [&](auto VARIANT) {
     constexpr int kVariant = decltype(VARIANT)::value;
     if constexpr (kVariant >= YUMA_VARIANT_YUMA3) {
       if (p.vector_form && p.w_u16)
         return with_bool(p.sc != 0, [&](auto SC) {
-          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K, B_move, rmask, rowmask);
+          launch_scan_as<kVariant, true, uint16_t, decltype(SC)::value>(st, p, A, sched, K, B_move, rmask, rowmask, B_rowstat, tpart);
         });
-      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K, B_move, rmask, rowmask);
+      if (p.vector_form && p.sc) return launch_scan_as<kVariant, true, float, true>(st, p, A, sched, K, B_move, rmask, rowmask, B_rowstat, tpart);
     }
     if (p.w_u16 || p.sc) bad_plan(p);
     with_bool(p.vector_form != 0, [&](auto VEC) {
-      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K, B_move, rmask, rowmask);
+      launch_scan_as<kVariant, decltype(VEC)::value, float, false>(st, p, A, sched, K, B_move, rmask, rowmask, B_rowstat, tpart);
     });
   });
 }
@@ -7629,6 +7866,17 @@ void read_rows(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_
   q->rows = rows_dev;
   q->n_rows = n_rows;
   q->B_rows = B_rows;
+}
+
+// yuma_run_rowstat / yuma_graph_create_rowstat: as read_rows, but n_rows = 0 with NULL rows_dev and B_rows is
+// "no row list"; and the summary output as given (run_plan refuses a NULL one; check_native a schedule or a
+// B_move beside it).
+void read_rowstat(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
+                  const int32_t* rows_dev, int n_rows, float* B_rows, float* B_rowstat, RunReq* q) {
+  read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, q);
+  if (n_rows == 0 && rows_dev == nullptr && B_rows == nullptr) q->has_rows = 0;
+  q->has_rowstat = 1;
+  q->B_rowstat = B_rowstat;
 }
 
 // yuma_run_resets / yuma_graph_create_resets: the event list as given (run_plan refuses what is wrong with it);
@@ -7789,6 +8037,28 @@ int yuma_run_rows(int variant, const yuma_params_t* params_dev, int N, int E, in
   if (const int err = read_opts(opts, &q)) return err;
   read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, &q);
   return run_direct(q);
+}
+
+size_t yuma_workspace_bytes_rowstat(int variant, int N, int E, int V, int M, int full_outputs) {
+  if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
+  return reset_table_offset(carve(nullptr, variant, N, E, V, M, full_outputs).bytes) + rowstat_part_bytes(N, E, V, M);
+}
+
+int yuma_run_rowstat(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                     const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                     const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
+                     float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows, float* B_rows,
+                     float* B_rowstat, void* workspace, size_t workspace_bytes, int chunk_epochs,
+                     const yuma_run_options_t* opts, void* stream, float* phase_ms) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, stream, phase_ms};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_rowstat(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, B_rowstat, &q);
+  return run_direct(q);
+}
+
+int yuma_rowstat_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
+  return rowstat_native(variant, N, E, V, M, out, flags) ? 1 : 0;
 }
 
 size_t yuma_workspace_bytes_resets(int variant, int N, int E, int V, int M, int full_outputs) {
@@ -7986,6 +8256,19 @@ int yuma_graph_create_rows(yuma_graph_t* graph, int variant, const yuma_params_t
            chunk_epochs, nullptr, nullptr};
   if (const int err = read_opts(opts, &q)) return err;
   read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, &q);
+  return graph_create_impl(graph, q);
+}
+
+int yuma_graph_create_rowstat(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
+                              int K, int V, int M, const float* W, const float* S, const int32_t* sched_dev,
+                              const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
+                              const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
+                              const int32_t* rows_dev, int n_rows, float* B_rows, float* B_rowstat, void* workspace,
+                              size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
+  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
+           chunk_epochs, nullptr, nullptr};
+  if (const int err = read_opts(opts, &q)) return err;
+  read_rowstat(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, B_rowstat, &q);
   return graph_create_impl(graph, q);
 }
 

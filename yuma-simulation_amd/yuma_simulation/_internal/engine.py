@@ -60,6 +60,10 @@ EXPORTED_SYMBOLS = (
     "yuma_run_rows",
     "yuma_rows_native",
     "yuma_graph_create_rows",
+    "yuma_workspace_bytes_rowstat",
+    "yuma_run_rowstat",
+    "yuma_rowstat_native",
+    "yuma_graph_create_rowstat",
     "yuma_workspace_bytes_resets",
     "yuma_run_resets",
     "yuma_resets_native",
@@ -283,6 +287,18 @@ def load_library(path: str | None = None):
             lib.yuma_graph_create_rows.restype = i32
             lib.yuma_rows_native.argtypes = [i32, i32, i32, i32, i32, i32, i32]
             lib.yuma_rows_native.restype = i32
+        # row summary: yuma_run_rows's arguments with B_rowstat after B_rows
+        if hasattr(lib, "yuma_run_rowstat"):  # (A/B libraries of older sources lack them)
+            a = lib.yuma_run_rows.argtypes
+            lib.yuma_run_rowstat.argtypes = a[:20] + [vp] + a[20:]
+            lib.yuma_run_rowstat.restype = i32
+            a = lib.yuma_graph_create_rows.argtypes
+            lib.yuma_graph_create_rowstat.argtypes = a[:21] + [vp] + a[21:]
+            lib.yuma_graph_create_rowstat.restype = i32
+            lib.yuma_workspace_bytes_rowstat.argtypes = [i32, i32, i32, i32, i32, i32]
+            lib.yuma_workspace_bytes_rowstat.restype = sz
+            lib.yuma_rowstat_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
+            lib.yuma_rowstat_native.restype = i32
         # reset events: yuma_run_opts's arguments, the list and its length after `out`
         if hasattr(lib, "yuma_run_resets"):  # (A/B libraries of older sources lack them)
             a = lib.yuma_run_opts.argtypes
@@ -578,6 +594,8 @@ class RunResult:
     B_move: torch.Tensor | None = None          # [E, N, 2]: max |B_t - B_{t-1}|, max |B_t| (run(want_move=True))
     B_rows: torch.Tensor | None = None          # [len(hist_epochs), N, len(watch_rows), M] (run(watch_rows=))
     watch_rows: tuple[int, ...] | None = None   # the validator row of each B_rows row
+    # [E, N, V, 3]: per validator max |B_t - B_{t-1}|, max |B_t|, sum B_t (run(want_row_stats=True))
+    B_rowstat: torch.Tensor | None = None
 
 
 def _as_dev(x: torch.Tensor, dev) -> torch.Tensor:
@@ -668,6 +686,27 @@ def move_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = 
     outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
     flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
     return bool(load_library().yuma_move_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
+
+
+def rowstat_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False,
+                   want: tuple[str, ...] = (), *, shared_inputs: bool = False, w_u16: bool = False) -> bool:
+    """Whether `run(..., want_row_stats=True)` with these arguments has the bond
+    scan form B_rowstat itself (yuma_rowstat_native; needs the library, not a
+    GPU): Yuma 3 / Yuma 4, any V, M % 4 == 0, fp32 weights, no shared inputs, no
+    history and none of Wn / Wc / Wb / B_inst / Tv wanted. Otherwise `run`
+    reduces a dense fp32 history and RunGraph refuses."""
+    names = {"Dn", "C", "I", "B_final", *want}
+    if want_hist:
+        names.add("B_hist")
+    outs = YumaOutputsC(**{k: (1 if k in names else None) for k in OUTPUT_FIELDS})
+    flags = (RUN_SHARED_INPUTS if shared_inputs else 0) | (RUN_W_U16 if w_u16 else 0)
+    return bool(load_library().yuma_rowstat_native(variant, N, E, V, M, ctypes.addressof(outs), flags))
+
+
+def workspace_bytes_rowstat(variant: int, N: int, E: int, V: int, M: int, full_outputs: bool = False) -> int:
+    """Workspace bytes of a run with the row summary (yuma_workspace_bytes_rowstat):
+    the run's own and a second array of quad partials for the row totals."""
+    return int(load_library().yuma_workspace_bytes_rowstat(variant, N, E, V, M, 1 if full_outputs else 0))
 
 
 def resets_native(variant: int, N: int, E: int, V: int, M: int, want_hist: bool = False,
@@ -863,6 +902,38 @@ def move_from_history(hist: torch.Tensor, B_init: torch.Tensor | None) -> torch.
         out[t0:t0 + step, :, 0] = (cur - prev).abs().amax((-2, -1))
         out[t0:t0 + step, :, 1] = cur.abs().amax((-2, -1))
     return out
+
+
+def rowstat_from_history(hist: torch.Tensor, B_init: torch.Tensor | None) -> torch.Tensor:
+    """B_rowstat [E, N, V, 3] of a dense fp32 history [E, N, V, M]: the two
+    amax(-1) expressions that define columns 0 and 1, and the fp32 sum(-1) as
+    column 2 (torch's order, not the scan's canonical one). A block of epochs at
+    a time, as move_from_history."""
+    E, N, V, M = hist.shape
+    out = torch.empty((E, N, V, 3), dtype=torch.float32, device=hist.device)
+    first = torch.zeros((1, N, V, M), dtype=torch.float32, device=hist.device) if B_init is None else B_init[None]
+    step = max(1, (1 << 26) // max(1, N * V * M))
+    for t0 in range(0, E, step):
+        cur = hist[t0:t0 + step]
+        prev = torch.cat([first if t0 == 0 else hist[t0 - 1:t0], cur[:-1]])
+        out[t0:t0 + step, :, :, 0] = (cur - prev).abs().amax(-1)
+        out[t0:t0 + step, :, :, 1] = cur.abs().amax(-1)
+        out[t0:t0 + step, :, :, 2] = cur.sum(-1)
+    return out
+
+
+def settled_epoch_rows(B_rowstat, tol: float, *, relative: bool = False) -> torch.Tensor:
+    """When each validator's bonds stopped moving: settled_epoch for rows.
+    B_rowstat is [E, ..., V, 3] (a RunResult's [E, N, V, 3], or one scenario's
+    [E, V, 3]; torch or numpy, on any device): for every index (n, v) the first
+    epoch t with B_rowstat[t', n, v, 0] <= tol for every t' >= t, or (relative)
+    <= tol * B_rowstat[t', n, v, 1]. E where no such t exists; a NaN entry
+    never counts as settled. Returns a CPU int64 tensor of shape
+    B_rowstat.shape[1:-1], [N, V]. Pure torch: needs neither the library nor a GPU."""
+    b = torch.as_tensor(B_rowstat).detach().to("cpu")
+    if b.dim() < 3 or b.shape[-1] != 3:
+        raise ValueError(f"B_rowstat shape {tuple(b.shape)} is not [E, ..., V, 3]")
+    return settled_epoch(b[..., :2], tol, relative=relative)
 
 
 def settled_epoch(B_move, tol: float, *, relative: bool = False) -> torch.Tensor:
@@ -1094,7 +1165,7 @@ def _vector_form(W: torch.Tensor, w_u16: bool, B_init, Wprev_init, o: dict, hist
 
 
 def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_inputs, hist_stride, hist_first,
-                hist_dtype, sched, watch=None, want_move=False):
+                hist_dtype, sched, watch=None, want_move=False, want_row_stats=False):
     """run's argument checks, in the order run has always raised them: the
     history type and the schedule before anything touches a GPU, the rest
     behind device(). Returns (dev, N, E, K, sched_host, h_epochs, watch_host);
@@ -1108,6 +1179,10 @@ def _check_args(params, W, S, B_init, Wprev_init, out, *, single_call, shared_in
         raise ValueError(f"want_move must be a bool, not {type(want_move).__name__}")
     if want_move and single_call:
         raise ValueError("single_call (yuma_epoch) takes no B_move: no want_move")
+    if not isinstance(want_row_stats, (bool, np.bool_)):
+        raise ValueError(f"want_row_stats must be a bool, not {type(want_row_stats).__name__}")
+    if want_row_stats and single_call:
+        raise ValueError("single_call (yuma_epoch) takes no B_rowstat: no want_row_stats")
     E, Nw, V, M = W.shape
     K = sched_host = None
     if sched is not None:  # validated before anything touches a GPU
@@ -1169,7 +1244,7 @@ _OUT_SHAPES = {
 
 
 def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None, move=None,
-            resets=None, rows=None, row_events=None) -> None:
+            resets=None, rows=None, row_events=None, rowstat=None) -> None:
     """The run's one launch: yuma_run_opts, yuma_run_sched under a native
     schedule, or yuma_run_watch with a native watch list (watch: the int32
     device list, B_watch and the buffer whose address the engine gets); with `capture`, their yuma_graph_create_* twins,
@@ -1181,8 +1256,15 @@ def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watc
     for yuma_run_rows (its watch list and B_move may both be absent).
     row_events: the int32 device row-event list [n, 4], for yuma_run_events
     (yuma_run_resets's arguments, the second list after the first, which may be
-    absent: NULL, 0)."""
-    if rows is not None:  # yuma_run_move's arguments (B_move may be NULL), the row list after B_move
+    absent: NULL, 0). rowstat: B_rowstat, for yuma_run_rowstat (yuma_run_rows's
+    arguments, B_rowstat after B_rows; no schedule and no B_move beside it, and
+    its watch and row lists may both be absent)."""
+    if rowstat is not None:
+        run_fn, graph_fn = lib.yuma_run_rowstat, lib.yuma_graph_create_rowstat
+        w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
+        rl = (None, 0, None) if rows is None else (rows[0].data_ptr(), rows[0].numel(), rows[2].data_ptr())
+        args = (head + (0,) + tail[:4] + (None,) + tail[4:7] + w + (None,) + rl + (rowstat.data_ptr(),) + tail[7:])
+    elif rows is not None:  # yuma_run_move's arguments (B_move may be NULL), the row list after B_move
         run_fn, graph_fn = lib.yuma_run_rows, lib.yuma_graph_create_rows
         w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
         args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
@@ -1231,7 +1313,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         phase_ms: list | None = None, capture: list | None = None,
         single_call: bool = False, shared_inputs: bool = False,
         hist_stride: int = 1, hist_first: int | None = None, hist_dtype=None, sched=None,
-        watch=None, want_move: bool = False, resets=None, watch_rows=None, row_resets=None) -> RunResult:
+        watch=None, want_move: bool = False, resets=None, watch_rows=None, row_resets=None,
+        want_row_stats: bool = False) -> RunResult:
     """E epochs of N scenarios. W [E,N,V,M], S [E,N,V] (raw); optional
     B_init [N,V,M] and (Yuma2) normalised Wprev_init [N,V,M].
     single_call: E == 1 through yuma_epoch (one call of a Yuma* variant,
@@ -1315,6 +1398,23 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     form, shared inputs, uint16 weights, the full-output matrices) that chain
     runs (extra["resets_path"] == "segments"; a captured run raises EngineError
     instead).
+    want_row_stats: the result's B_rowstat [E, N, V, 3] (fp32, on the device)
+    holds per epoch, scenario and validator max over m of |B_t - B_{t-1}|, max
+    over m of |B_t| and sum over m of B_t, B_t as for want_move: columns 0 and
+    1 are bit-equal to (hist[t] - hist[t-1]).abs().amax(-1) and
+    hist[t].abs().amax(-1) on the dense fp32 history, and their amax over v is
+    B_move; every other output keeps its bits (settled_epoch_rows reads it).
+    Where rowstat_native holds, W is not uint16, no history, schedule or
+    want_move rides in the same run and the buffers have the vector form's
+    alignment, the history-less scan forms it (yuma_run_rowstat,
+    extra["rowstat_path"] == "native"): column 2 is then summed in the
+    canonical order of the dividends (include/yuma_hip.h) and has the same bits
+    for every chunk_epochs and scan shape. Elsewhere the run writes a dense
+    fp32 history and reduces it on the device, column 2 as the fp32 sum(-1),
+    and drops the history unless asked for (extra["rowstat_path"] == "dense"; a
+    captured run raises EngineError instead). watch= and watch_rows= combine
+    with the native path; resets= and row_resets= do not combine at all
+    (ValueError).
     watch_rows: a non-empty sequence or integer tensor of validator indices
     (duplicates and any order allowed; validated on the host, ValueError): the
     result's B_rows [n_hist, N, len(watch_rows), M] is the fp32 bond history of
@@ -1362,6 +1462,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
             raise ValueError("resets= takes Yuma 3 / Yuma 4 only")
         for name, given in (("sched", sched is not None), ("watch_rows", watch_rows is not None),
                             ("watch", watch is not None), ("want_move", bool(want_move)),
+                            ("want_row_stats", bool(want_row_stats)),
                             ("single_call", bool(single_call)), ("hist_dtype=torch.bfloat16", h_bf16)):
             if given:
                 raise ValueError(f"resets= does not combine with {name}")
@@ -1376,6 +1477,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
             raise ValueError("row_resets= takes Yuma 3 / Yuma 4 only")
         for name, given in (("sched", sched is not None), ("watch_rows", watch_rows is not None),
                             ("watch", watch is not None), ("want_move", bool(want_move)),
+                            ("want_row_stats", bool(want_row_stats)),
                             ("single_call", bool(single_call)), ("hist_dtype=torch.bfloat16", h_bf16)):
             if given:
                 raise ValueError(f"row_resets= does not combine with {name}")
@@ -1389,15 +1491,19 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
     dev, N, E, K, sched_host, h_epochs, watch_host = _check_args(
         params, W, S, B_init, Wprev_init, out, single_call=single_call, shared_inputs=shared_inputs,
         hist_stride=hist_stride, hist_first=hist_first, hist_dtype=hist_dtype, sched=sched, watch=watch,
-        want_move=want_move)
+        want_move=want_move, want_row_stats=want_row_stats)
     V, M = W.shape[2:]
     lib = load_library()
     W_arg, S_arg = W, S  # as given: the code below rebinds W and S (widened, moved, expanded under a schedule)
 
     def move_dense():
-        """B_move from a dense fp32 history of the same run, on the inputs and
+        """B_move (and / or B_rowstat) from a dense fp32 history of the same run, on the inputs and
         the schedule as the caller gave them; the history asked for (its stride,
         its type, the caller's buffer) and B_watch from it."""
+        if capture is not None and want_row_stats:
+            raise EngineError("a captured run cannot reduce a dense history: want_row_stats needs "
+                              "rowstat_native(variant, N, E, V, M, ...), fp32 weights, no history, schedule or "
+                              "want_move in the same run and vector-aligned buffers")
         if capture is not None:
             raise EngineError("a captured run cannot reduce a dense history: want_move needs "
                               "move_native(variant, N, E, V, M, ...), no history in the same run and "
@@ -1406,8 +1512,12 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         r = run(variant, params, W_arg, S_arg, B_init, Wprev_init, want_hist=True, want=want, chunk_epochs=chunk_epochs,
                 workspace=workspace, out=o_in or None, phase_ms=phase_ms, shared_inputs=shared_inputs, sched=sched)
         dense = r.B_hist
-        r.B_move = move_from_history(dense, None if B_init is None else _as_dev(B_init, dev))
-        r.extra["move_path"] = "dense"
+        if want_move:
+            r.B_move = move_from_history(dense, None if B_init is None else _as_dev(B_init, dev))
+            r.extra["move_path"] = "dense"
+        if want_row_stats:
+            r.B_rowstat = rowstat_from_history(dense, None if B_init is None else _as_dev(B_init, dev))
+            r.extra["rowstat_path"] = "dense"
         slots = torch.as_tensor(h_epochs, dtype=torch.int64, device=dev)
         hist_user = (out or {}).get("B_hist")
         r.B_hist, r.hist_epochs = None, None
@@ -1463,6 +1573,11 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         return segments()
     if want_move and (want_hist or (out or {}).get("B_hist") is not None
                       or not move_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs)):
+        return move_dense()
+    # the row summary: native alone; beside a history, a schedule, B_move or uint16 weights it is reduced
+    if want_row_stats and (want_hist or (out or {}).get("B_hist") is not None or want_move or sched is not None
+                           or W.dtype == torch.uint16
+                           or not rowstat_native(variant, N, E, V, M, False, out_names, shared_inputs=shared_inputs)):
         return move_dense()
     # a watch list the engine does not take natively rides on an fp32 history of the run's own
     watch_dense = watch_host is not None and (
@@ -1538,8 +1653,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                 raise EngineError("a captured run cannot expand its inputs: sched= needs "
                                   "sched_native(variant, N, E, K, V, M, ...) and vector-aligned buffers")
             W, S = _take_slices(W, sched_host.to(dev)), _take_slices(S, sched_host.to(dev))
-    if want_move and not _vector_form(W, w_u16, B_init, Wprev_init, o, False):  # (nothing is launched yet)
-        return move_dense()
+    if (want_move or want_row_stats) and not _vector_form(W, w_u16, B_init, Wprev_init, o, False):
+        return move_dense()  # (nothing is launched yet)
     resets_dev = None
     rowev_dev = None
     if row_resets is not None:
@@ -1559,6 +1674,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         else:
             resets_dev = resets_host.to(device=dev, dtype=torch.int32)
     b_move = torch.empty((E, N, 2), dtype=torch.float32, device=dev) if want_move else None  # (the engine zeroes it)
+    b_rowstat = torch.empty((E, N, V, 3), dtype=torch.float32, device=dev) if want_row_stats else None  # (likewise)
     watch_arg = None
     if watch_host is not None and not watch_dense:
         if (isinstance(watch, torch.Tensor) and watch.device == dev and watch.dtype == torch.int32
@@ -1580,7 +1696,9 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         # (no stored epoch: nothing is written, but the engine refuses a null B_rows)
         rows_arg = (rows_dev, b_rows, b_rows if h_epochs else torch.empty(4, dtype=torch.float32, device=dev))
     full = o.get("Tv") is not None
-    if sched_dev is not None:
+    if b_rowstat is not None:
+        nbytes = workspace_bytes_rowstat(variant, N, E, V, M, full)
+    elif sched_dev is not None:
         nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
     elif rowev_dev is not None and rowev_dev.shape[0] > 0:
         nbytes = int(lib.yuma_workspace_bytes_events(variant, N, E, V, M, 1 if full else 0))
@@ -1606,7 +1724,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                 (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
                  workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
                 capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move, resets=resets_dev, rows=rows_arg,
-                row_events=rowev_dev)
+                row_events=rowev_dev, rowstat=b_rowstat)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -1617,6 +1735,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         keep["sched"] = sched_dev
     if want_move:
         keep["move_path"] = "native"
+    if want_row_stats:
+        keep["rowstat_path"] = "native"
     if resets is not None:  # how the events were applied: by the bond scan, or by cutting the run
         keep["resets_path"] = "native"
         keep["resets"] = resets_dev
@@ -1628,7 +1748,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         hist = hist.to(torch.bfloat16) if hist_user is None else hist_user.copy_(hist)
     if watch_host is None and rows_host is None:
         return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, None if hist is None else h_epochs,
-                         B_move=b_move)
+                         B_move=b_move, B_rowstat=b_rowstat)
     if (watch_dense or rows_dense) and not hist_asked:  # the history was the run's own: dropped
         hist = None
     if watch_host is None:
@@ -1647,7 +1767,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
             b_rows = o["B_hist"].index_select(2, rows_host.to(dev)).contiguous()
     return RunResult(o["Dn"], o["C"], o["I"], o["B_final"], hist, keep, h_epochs, b_watch,
                      None if watch_host is None else tuple(int(c) for c in watch_host.tolist()), B_move=b_move,
-                     B_rows=b_rows, watch_rows=None if rows_host is None else tuple(int(c) for c in rows_host.tolist()))
+                     B_rows=b_rows, watch_rows=None if rows_host is None else tuple(int(c) for c in rows_host.tolist()),
+                     B_rowstat=b_rowstat)
 
 
 class RunGraph:

@@ -94,7 +94,7 @@ def _reward_key(config: YumaConfig) -> tuple:
 def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                     want_incentives: bool = True, bonds_every: int = 1, bonds_dtype=None,
                     dedup_inputs: bool = False, bonds_columns=None, bonds_movement: bool = False,
-                    bond_resets=None, bonds_validators=None, validator_resets=None):
+                    bond_resets=None, bonds_validators=None, validator_resets=None, bonds_row_stats: bool = False):
     """Run many simulations; runs that share (variant, E, V, M) go to the
     device as one batched engine call. Returns one (dividends, bonds, incentives)
     tuple per run, in order.
@@ -162,9 +162,22 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
     3.x / Yuma 4 is a ValueError, never silently ignored. Combines with
     bond_resets and bonds_every; not with dedup_inputs, bonds_columns,
     bonds_validators, bonds_movement or bonds_dtype=torch.bfloat16
+    (ValueError).
+    bonds_row_stats: each run's tuple gains a last element (behind the
+    movement's, where bonds_movement is given too), a [E, V, 3] CPU fp32
+    tensor: per epoch and validator the largest |B_t - B_{t-1}| and the
+    largest |B_t| over the validator's bond row, and the row's sum
+    (engine.run's want_row_stats; engine.settled_epoch_rows reads it: which
+    validator settled when). Every epoch is covered whatever bonds_every says.
+    With want_bonds=False, Yuma 3 / Yuma 4 runs whose miner count is a multiple
+    of 4 (engine.rowstat_native) keep no bond history at all; otherwise it is
+    reduced from the run's history on the device. The other elements keep the
+    default call's bits. Does not combine with bond_resets or validator_resets
     (ValueError)."""
     if operator.index(bonds_every) < 1:
         raise ValueError(f"bonds_every={bonds_every} must be at least 1")
+    if bonds_row_stats and (bond_resets is not None or validator_resets is not None):
+        raise ValueError("bonds_row_stats does not combine with bond_resets or validator_resets")
     if bonds_dtype not in (None, torch.float32, torch.bfloat16):
         raise ValueError(f"bonds_dtype={bonds_dtype} must be None, torch.float32 or torch.bfloat16")
     if bonds_columns is not None:  # validated on the host, before anything touches a GPU
@@ -208,7 +221,8 @@ def run_simulations(runs: list[SimulationRun], *, want_bonds: bool = True,
                                 bonds_dtype=bonds_dtype, dedup_inputs=bool(dedup_inputs),
                                 bonds_columns=bonds_columns, bonds_movement=bool(bonds_movement),
                                 bond_resets=bond_resets, bonds_validators=bonds_validators,
-                                **({"validator_resets": validator_resets} if validator_resets is not None else {}))
+                                **({"validator_resets": validator_resets} if validator_resets is not None else {}),
+                                **({"bonds_row_stats": True} if bonds_row_stats else {}))
 
 
 def _check_validator_resets(runs, validator_resets) -> list:
@@ -326,7 +340,7 @@ def _prefix_total(cs: np.ndarray, E: int, n: int):
 def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentives: bool,
                      totals: bool = False, bonds_every: int = 1, bonds_dtype=None, dedup_inputs: bool = False,
                      bonds_columns=None, bonds_movement: bool = False, bond_resets=None, bonds_validators=None,
-                     validator_resets=None):
+                     validator_resets=None, bonds_row_stats: bool = False):
     """totals: each run's dividends as the sums of its first case.num_epochs
     per-epoch values, one per validator in case.validators order (the sheet's
     totals, the same bits as summing the lists) instead of the per-epoch
@@ -383,6 +397,7 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
             hist_dtype=bonds_dtype if dense else None, watch=watch,
             **({"watch_rows": rows} if rows is not None else {}),
             **({"want_move": True} if bonds_movement else {}), **({"resets": events} if events else {}),
+            **({"want_row_stats": True} if bonds_row_stats else {}),
             **({"row_resets": row_events} if row_events else {}))))
     for E, V, idx, S, res in launched:
         Dn = res.Dn.cpu()
@@ -395,6 +410,7 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
             hist = res.B_hist.cpu()
         inc = res.I.cpu() if want_incentives else None
         move = res.B_move.cpu() if bonds_movement else None
+        rowstat = res.B_rowstat.cpu() if bonds_row_stats else None
         # the dividend ratio of the whole group in one pass of the same
         # elementwise ops when its runs share the reward scalars (the sheet)
         ratio = None
@@ -425,6 +441,8 @@ def _run_simulations(runs: list[SimulationRun], want_bonds: bool, want_incentive
             bonds = [hist[e, j].clone().to(home) for e in range(hist.shape[0])] if want_bonds else []
             incentives = [inc[e, j].clone().to(home) for e in range(E)] if want_incentives else []
             results[k] = (div, bonds, incentives, move[:, j].clone()) if bonds_movement else (div, bonds, incentives)
+            if bonds_row_stats:
+                results[k] = results[k] + (rowstat[:, j].clone(),)
     return results
 
 
