@@ -101,8 +101,9 @@ __device__ __forceinline__ float nan_to_num(float x, float nan_v = 0.0f) {
 // q = RN(a r); e = fma(-d, q, a) (exact); q' = RN(q + e r) is RN(a/d)
 // (Markstein) as long as nothing underflows or overflows. Guard: |d| and |a|
 // in [2^-60, 2^60] (or a = +-0, where q already carries the right sign); any
-// other operand takes the IEEE division. Checked bitwise against IEEE fp32
-// division on 7.9e8 random pairs (tools/README: divtest).
+// other operand takes the IEEE division. Held bitwise to IEEE fp32 division
+// on and around the guard, through every kernel form that divides, by
+// tests/test_gpu_division_forms.py (inputs: tests/division_cases.py).
 struct RowDiv {
   float d, r;
   bool ok;
