@@ -11,6 +11,9 @@
  * The entry points below replace exactly those two seams:
  *   yuma_epoch  <- one call of a Yuma* variant (E = 1, every output optional)
  *   yuma_run    <- the whole epoch loop of run_simulation (E epochs, N scenarios)
+ * Every run is one yuma_request_t (below) given to yuma_run_request or
+ * yuma_graph_create_request; the positional entry points are shims that fill
+ * that record from their arguments.
  * The Python mirror (yuma_simulation/_internal/engine.py) binds them with
  * ctypes; INTEGRATION.md shows the binding a maintainer adds to the reference.
  *
@@ -259,7 +262,8 @@ int yuma_hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_ou
  *
  * Simulated inputs are piecewise constant (every case of cases.py holds a
  * handful of matrices for tens of epochs; a convergence study holds one for
- * thousands). yuma_run_sched takes the K distinct slices once, W [K][N][V][M]
+ * thousands). A request with a schedule (sched_dev != NULL or K != 0; the one
+ * without the other is YUMA_EINVAL) takes the K distinct slices once, W [K][N][V][M]
  * (uint16 under YUMA_RUN_W_U16) and S [K][N][V], and a schedule sched_dev [E]
  * in DEVICE memory: epoch t reads slice sched_dev[t]. Every output has the
  * bits of yuma_run_opts on the expanded inputs W'[t] = W[sched[t]],
@@ -293,6 +297,8 @@ int yuma_hist_bf16_native(int variant, int N, int E, int V, int M, const yuma_ou
  * rewrite it in place between replays like any other input.
  * ---------------------------------------------------------------------- */
 size_t yuma_workspace_bytes_sched(int variant, int N, int E, int K, int V, int M, int full_outputs);
+/* The request of yuma_run_opts with K and sched_dev, both mandatory: K < 1, then
+ * a NULL sched_dev are refused (YUMA_EINVAL) right after the options. */
 int yuma_run_sched(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
                    const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
                    const float* Wprev_init, const yuma_outputs_t* out, void* workspace,
@@ -307,8 +313,8 @@ int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma
  *
  * The charts that read a bond history plot a handful of servers (miner
  * columns); a [V][M] history per stored epoch is hundreds of times what they
- * read. yuma_run_watch takes a list watch_dev [n_watch] of miner columns in
- * DEVICE memory and writes B_watch [n_hist][N][V][n_watch] (fp32), n_hist =
+ * read. YUMA_REQ_WATCH: a list watch_dev [n_watch] of miner columns in
+ * DEVICE memory; the run writes B_watch [n_hist][N][V][n_watch] (fp32), n_hist =
  * yuma_hist_slots(E, stride, first) under the options' history stride and
  * first epoch, which apply to it as they do to B_hist: slot s, column j holds
  * the bits the dense history holds at [epoch t_s][n][v][watch_dev[j]].
@@ -320,10 +326,9 @@ int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma
  * only; B_watch is fp32. Every other output, B_final included, has the bits of
  * the same run without a watch list.
  *
- * The arguments are yuma_run_sched's with watch_dev, n_watch and B_watch after
- * `out`. sched_dev == NULL with K == 0 means no schedule: W is [E][N][V][M],
+ * sched_dev == NULL with K == 0 means no schedule: W is [E][N][V][M],
  * S [E][N][V] and the workspace yuma_workspace_bytes. With a schedule they are
- * exactly yuma_run_sched's and the workspace is yuma_workspace_bytes_sched.
+ * the schedule's and the workspace is yuma_workspace_bytes_sched.
  * The watch list needs no workspace of its own.
  *
  * Native (yuma_watch_native returns 1; host only, `flags` are the run's
@@ -341,7 +346,7 @@ int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma
  * any other input.
  *
  * Refusals, in this order, all before the first launch and without a HIP call
- * (yuma_graph_create_watch: the same code and yuma_last_error text, before the
+ * (the graph form: the same code and yuma_last_error text, before the
  * capture opens): the options (as yuma_run_opts); [the graph handle]; sizes;
  * NULL params / W / S / out / workspace; a schedule pointer with K < 1, or
  * K != 0 without one (YUMA_EINVAL); n_watch < 1, then a NULL watch_dev or
@@ -349,6 +354,8 @@ int yuma_sched_native(int variant, int N, int E, int K, int V, int M, const yuma
  * watch list not native (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and
  * YUMA_RUN_W_U16 as ever. yuma_epoch and yuma_shard_stage take no watch list.
  * ---------------------------------------------------------------------- */
+/* The request of yuma_run_sched's arguments (the schedule optional: NULL and
+ * K = 0) with YUMA_REQ_WATCH always set: an empty list is refused. */
 int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
                    const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
                    const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
@@ -359,8 +366,8 @@ int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int 
 /* ------------------------------------------------------------------------
  * Bond movement per epoch: when did the bonds stop moving.
  *
- * yuma_run_move writes B_move [E][N][2] (fp32, device memory) beside the
- * run's other outputs:
+ * YUMA_REQ_MOVE: the run writes B_move [E][N][2] (fp32, device memory) beside
+ * its other outputs:
  *   B_move[t][n][0] = max over (v, m) of |B_t[n][v][m] - B_{t-1}[n][v][m]|
  *   B_move[t][n][1] = max over (v, m) of |B_t[n][v][m]|
  * B_t is the bond state after epoch t, exactly the bits the dense fp32 history
@@ -382,10 +389,6 @@ int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int 
  * itself with a small kernel on the run's stream (inside a captured graph too:
  * every replay starts from zero). B_move needs no workspace of its own.
  *
- * The arguments are yuma_run_watch's with B_move after B_watch. n_watch == 0
- * with NULL watch_dev and NULL B_watch means "no watch list" (here only:
- * yuma_run_watch still refuses it).
- *
  * Native (yuma_move_native returns 1; host only, makes no HIP call; of `out`
  * it reads only which pointers are non-NULL; `flags` are the run's flags):
  * Yuma 3 and Yuma 4 (scalar or liquid alpha, any reset mode), the vector form
@@ -399,16 +402,18 @@ int yuma_watch_native(int variant, int N, int E, int V, int M, int n_watch, int 
  * first launch and the caller reduces an fp32 history itself.
  *
  * Refusals, in this order, all before the first launch and without a HIP call
- * (yuma_graph_create_move: the same code and yuma_last_error text, before the
+ * (the graph form: the same code and yuma_last_error text, before the
  * capture opens): the options (as yuma_run_opts); [the graph handle]; sizes;
  * NULL params / W / S / out / workspace; a schedule pointer with K < 1, or
- * K != 0 without one (YUMA_EINVAL); with a watch list (n_watch != 0 or either
- * pointer given), n_watch < 1, then a NULL watch_dev or B_watch (YUMA_EINVAL);
+ * K != 0 without one (YUMA_EINVAL); with a watch list (YUMA_REQ_WATCH),
+ * n_watch < 1, then a NULL watch_dev or B_watch (YUMA_EINVAL);
  * a NULL B_move (YUMA_EINVAL); the workspace size; the schedule not native;
  * the watch list not native; the movement not native, then not in vector form
  * (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and YUMA_RUN_W_U16 as ever.
  * yuma_epoch, yuma_shard_stage and the older entry points take no B_move.
  * ---------------------------------------------------------------------- */
+/* yuma_run_watch's request with B_move and YUMA_REQ_MOVE always set (a NULL B_move is refused); YUMA_REQ_WATCH
+ * is set when n_watch != 0 or either watch pointer is given: (NULL, 0, NULL) means "no watch list". */
 int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
                   const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
                   const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
@@ -421,8 +426,8 @@ int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs
  *
  * The other half of the watch list's question: where are validator v's bonds
  * across all miners, and which miners pay it (D[v] = sum over m of B[v][m]
- * I[m])? yuma_run_rows takes a list rows_dev [n_rows] of validator indices in
- * DEVICE memory and writes B_rows [n_hist][N][n_rows][M] (fp32), n_hist =
+ * I[m])? YUMA_REQ_ROWS: a list rows_dev [n_rows] of validator indices in
+ * DEVICE memory; the run writes B_rows [n_hist][N][n_rows][M] (fp32), n_hist =
  * yuma_hist_slots(E, stride, first) under the options' history stride and
  * first epoch: slot s, row j holds the bits the dense history holds at
  * [epoch t_s][n][rows_dev[j]][0 .. M). Duplicated and unsorted rows are
@@ -433,11 +438,6 @@ int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs
  * written. YUMA_RUN_HIST_BF16 concerns B_hist only; B_rows is fp32. Every
  * other output, B_final included, has the bits of the same run without a row
  * list. The row list needs no workspace of its own.
- *
- * The arguments are yuma_run_move's with rows_dev, n_rows and B_rows after
- * B_move. Here B_move == NULL means "no movement output" (yuma_run_move keeps
- * refusing NULL), and n_watch == 0 with NULL watch_dev and NULL B_watch means
- * "no watch list" as there. The row list is mandatory.
  *
  * Native (yuma_rows_native returns 1; host only, makes no HIP call; `flags`
  * are the run's flags): Yuma 3 and Yuma 4 (scalar or liquid alpha, any reset
@@ -456,18 +456,20 @@ int yuma_move_native(int variant, int N, int E, int V, int M, const yuma_outputs
  * replays like any other input.
  *
  * Refusals, in this order, all before the first launch and without a HIP call
- * (yuma_graph_create_rows: the same code and yuma_last_error text, before the
+ * (the graph form: the same code and yuma_last_error text, before the
  * capture opens): the options (as yuma_run_opts); [the graph handle]; sizes;
  * NULL params / W / S / out / workspace; a schedule pointer with K < 1, or
- * K != 0 without one (YUMA_EINVAL); with a watch list (n_watch != 0 or either
- * pointer given), n_watch < 1, then a NULL watch_dev or B_watch (YUMA_EINVAL);
+ * K != 0 without one (YUMA_EINVAL); with a watch list (YUMA_REQ_WATCH),
+ * n_watch < 1, then a NULL watch_dev or B_watch (YUMA_EINVAL);
  * n_rows < 1, then a NULL rows_dev or B_rows, then a grid of N n_rows
  * ceil(M / 64) blocks beyond INT_MAX (YUMA_EINVAL); the workspace size; the
- * schedule not native; the watch list not native; with a B_move, the movement
- * not native, then not in vector form; the row list not native
+ * schedule not native; the watch list not native; with YUMA_REQ_MOVE, the
+ * movement not native, then not in vector form; the row list not native
  * (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and YUMA_RUN_W_U16 as ever.
  * yuma_epoch, yuma_shard_stage and the older entry points take no row list.
  * ---------------------------------------------------------------------- */
+/* yuma_run_move's request with the row list and YUMA_REQ_ROWS always set (an empty list is refused); YUMA_REQ_MOVE
+ * is set when B_move != NULL (NULL means "no movement output"), YUMA_REQ_WATCH as in yuma_run_move. */
 int yuma_run_rows(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
                   const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
                   const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
@@ -480,8 +482,8 @@ int yuma_rows_native(int variant, int N, int E, int V, int M, int n_rows, int fl
  * Per-validator bond summary per epoch: which validator's bonds still move,
  * how large is each validator's position, when did each one settle.
  *
- * yuma_run_rowstat writes B_rowstat [E][N][V][3] (fp32, device memory) beside
- * the run's other outputs. B_t is the bond state after epoch t, exactly the
+ * YUMA_REQ_ROWSTAT: the run writes B_rowstat [E][N][V][3] (fp32, device memory)
+ * beside its other outputs. B_t is the bond state after epoch t, exactly the
  * bits the dense fp32 history holds; B_{-1} is B_init, or zeros without one.
  *   B_rowstat[t][n][v][0] = max over m of |B_t[n][v][m] - B_{t-1}[n][v][m]|
  *   B_rowstat[t][n][v][1] = max over m of |B_t[n][v][m]|
@@ -510,11 +512,8 @@ int yuma_rows_native(int variant, int N, int E, int V, int M, int n_rows, int fl
  * workspace (yuma_workspace_bytes_rowstat >= yuma_workspace_bytes) and a twin
  * of the dividends' summing kernel.
  *
- * The arguments are yuma_run_rows's with B_rowstat after B_rows. The row list
- * is optional here: n_rows == 0 with NULL rows_dev and NULL B_rows means "no
- * row list" (here only), and the watch list likewise as in yuma_run_move.
- * Watch and row lists are kernels of their own and combine. A schedule
- * pointer or a B_move does not: YUMA_EUNSUPPORTED.
+ * Watch and row lists are kernels of their own and combine with the summary. A
+ * schedule pointer or YUMA_REQ_MOVE does not: YUMA_EUNSUPPORTED.
  *
  * Native (yuma_rowstat_native returns 1; host only, makes no HIP call; of
  * `out` it reads only which pointers are non-NULL; `flags` are the run's
@@ -530,15 +529,17 @@ int yuma_rows_native(int variant, int N, int E, int V, int M, int n_rows, int fl
  * (FLAT1 / FLAT2) and not the summary form.
  *
  * Refusals, in this order, all before the first launch and without a HIP call
- * (yuma_graph_create_rowstat: the same code and yuma_last_error text, before
- * the capture opens): as yuma_run_rows up to the row list's (which apply only
- * when a row list is given); a NULL B_rowstat (YUMA_EINVAL); the workspace
+ * (the graph form: the same code and yuma_last_error text, before
+ * the capture opens): as the row list's section up to the row list's own (which
+ * apply only with YUMA_REQ_ROWS); a NULL B_rowstat (YUMA_EINVAL); the workspace
  * size (yuma_workspace_bytes_rowstat); the schedule, watch list, movement and
  * row list refusals of yuma_run_rows; a schedule pointer, a B_move or reset
  * events beside the summary; the summary not native; then not in vector form
  * (YUMA_EUNSUPPORTED); then YUMA_RUN_HIST_BF16 and YUMA_RUN_W_U16 as ever.
  * ---------------------------------------------------------------------- */
 size_t yuma_workspace_bytes_rowstat(int variant, int N, int E, int V, int M, int full_outputs);
+/* yuma_run_rows's request with B_rowstat and YUMA_REQ_ROWSTAT always set (a NULL B_rowstat is refused); here
+ * YUMA_REQ_ROWS too is set only when n_rows != 0 or either row pointer is given. */
 int yuma_run_rowstat(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
                      const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
                      const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev,
@@ -552,7 +553,7 @@ int yuma_rowstat_native(int variant, int N, int E, int V, int M, const yuma_outp
  *
  * A subnet deregisters miners all the time, and every deregistration clears
  * that UID's bonds; yuma_params_t carries one reset per scenario and run.
- * yuma_run_resets takes a list events_dev [n_events] of yuma_reset_event_t in
+ * YUMA_REQ_RESETS: a list events_dev [n_events] of yuma_reset_event_t in
  * DEVICE memory. An event (epoch t, scenario n, column c, mode) applies
  * B[n][:, c] = 0 before epoch t's update of scenario n, if a bond state exists
  * and the mode's rule holds:
@@ -575,9 +576,8 @@ int yuma_rowstat_native(int variant, int N, int E, int V, int M, const yuma_outp
  * zeroed; the result does not depend on chunk_epochs (an event at a chunk's
  * first epoch reads C of the previous chunk's last epoch).
  *
- * The arguments are yuma_run_opts's with events_dev and n_events after `out`.
- * n_events == 0 with a NULL list is exactly yuma_run_opts: the same launches
- * and the yuma_workspace_bytes size. Otherwise the workspace is
+ * Without the section the run is exactly yuma_run_opts: the same launches
+ * and the yuma_workspace_bytes size. With it the workspace is
  * yuma_workspace_bytes_resets (>= yuma_workspace_bytes): the difference is a
  * table of one bit per (epoch, scenario, column), bytes [E][N][ceil(M / 8)],
  * which the engine zeroes with a small kernel and a resolve kernel (one thread
@@ -595,16 +595,17 @@ int yuma_rowstat_native(int variant, int N, int E, int V, int M, const yuma_outp
  * requested; the fp32 history dense, strided or absent -- the calls whose scan
  * is YUMA_ELEM_WIDE, YUMA_ELEM_TILE_HIST, YUMA_ELEM_FLAT1 or YUMA_ELEM_FLAT2.
  * Elsewhere the entry points return YUMA_EUNSUPPORTED before the first launch
- * and the caller cuts the run at the event epochs itself. Schedules, watch
- * lists and B_move are not taken by these entry points.
+ * and the caller cuts the run at the event epochs itself. Events (of either
+ * kind) beside a schedule, a watch list, B_move, a row list or the row summary
+ * have never run: a request that asks for both is YUMA_EUNSUPPORTED.
  *
  * Refusals, in this order, all before the first launch and without a HIP call
- * (yuma_graph_create_resets: the same code and yuma_last_error text, before
+ * (the graph form: the same code and yuma_last_error text, before
  * the capture opens): the options (as yuma_run_opts); [the graph handle];
  * sizes; NULL params / W / S / out / workspace; n_events < 0, then
  * n_events > 0 with a NULL list (YUMA_EINVAL); the workspace size
- * (YUMA_EWORKSPACE); the events not native, then not in vector form
- * (YUMA_EUNSUPPORTED).
+ * (YUMA_EWORKSPACE); a section the events do not combine with; the events not
+ * native, then not in vector form (YUMA_EUNSUPPORTED).
  * ---------------------------------------------------------------------- */
 typedef struct yuma_reset_event {
   int32_t epoch;    /* the reset precedes this epoch's update                  */
@@ -613,6 +614,8 @@ typedef struct yuma_reset_event {
   int32_t mode;     /* YUMA_RESET_ALWAYS or YUMA_RESET_IF_ZERO_CONSENSUS       */
 } yuma_reset_event_t; /* 16 bytes */
 size_t yuma_workspace_bytes_resets(int variant, int N, int E, int V, int M, int full_outputs);
+/* yuma_run_opts's request with the event list; YUMA_REQ_RESETS is set when n_events != 0 or events_dev != NULL:
+ * (NULL, 0) means "no events". */
 int yuma_run_resets(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                     const float* W, const float* S, const float* B_init, const float* Wprev_init,
                     const yuma_outputs_t* out, const yuma_reset_event_t* events_dev, int n_events,
@@ -624,9 +627,8 @@ int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outpu
  * Validator-row events: bond rows zeroed at any epoch inside one run.
  *
  * A validator that leaves or whose hotkey is replaced has its bond row
- * cleared. yuma_run_events is yuma_run_resets with a second list,
- * row_events_dev [n_row_events] of yuma_row_event_t in DEVICE memory, after
- * n_events. A row event (epoch t, scenario n, row v) applies B[n][v][:] = 0
+ * cleared. YUMA_REQ_ROW_EVENTS: a second list, row_events_dev [n_row_events]
+ * of yuma_row_event_t in DEVICE memory, with or without YUMA_REQ_RESETS. A row event (epoch t, scenario n, row v) applies B[n][v][:] = 0
  * before epoch t's update of scenario n, if a bond state exists (t >= 1, or
  * t == 0 and B_init is given):
  *  - the event is unconditional: no consensus rule applies to a validator;
@@ -643,9 +645,9 @@ int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outpu
  * resumed from the previous B_final with the rows and columns zeroed; the
  * result does not depend on chunk_epochs.
  *
- * n_row_events == 0 with a NULL list is exactly yuma_run_resets: the same
- * launches and the same workspace requirement (with n_events == 0 and a NULL
- * list as well, yuma_run_opts's). Otherwise the workspace is
+ * Without the section the run is exactly that of YUMA_REQ_RESETS alone: the same
+ * launches and the same workspace requirement (without either section,
+ * yuma_run_opts's). With it the workspace is
  * yuma_workspace_bytes_events (>= yuma_workspace_bytes_resets): the difference
  * is the row table, one 32-BIT WORD per (epoch, scenario, validator), words
  * [E][N][V] -- the index of the scan's other per-row inputs -- padded to 256
@@ -665,7 +667,7 @@ int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outpu
  * N * V >= 2^29 with a row list (YUMA_EUNSUPPORTED: the scan steps through the
  * row table by one epoch's N * V words as a 32-bit count of bytes; such a run's
  * row table alone exceeds 2 GiB per epoch). All come before the first
- * launch and without a HIP call (yuma_graph_create_events: the same code and
+ * launch and without a HIP call (the graph form: the same code and
  * yuma_last_error text, before the capture opens).
  * ---------------------------------------------------------------------- */
 typedef struct yuma_row_event {
@@ -675,6 +677,8 @@ typedef struct yuma_row_event {
   int32_t reserved; /* must be 0                              */
 } yuma_row_event_t; /* 16 bytes */
 size_t yuma_workspace_bytes_events(int variant, int N, int E, int V, int M, int full_outputs);
+/* yuma_run_resets's request with the row event list after n_events; YUMA_REQ_ROW_EVENTS is set when
+ * n_row_events != 0 or row_events_dev != NULL. */
 int yuma_run_events(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                     const float* W, const float* S, const float* B_init, const float* Wprev_init,
                     const yuma_outputs_t* out, const yuma_reset_event_t* events_dev, int n_events,
@@ -682,6 +686,76 @@ int yuma_run_events(int variant, const yuma_params_t* params_dev, int N, int E, 
                     void* workspace, size_t workspace_bytes, int chunk_epochs,
                     const yuma_run_options_t* opts, void* stream, float* phase_ms);
 int yuma_events_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags);
+
+/* ------------------------------------------------------------------------
+ * The run request: one record behind every run and graph entry point.
+ *
+ * A run is the base fields (what yuma_run_opts takes, and a schedule) plus any
+ * of six sections, each described in its block above. A section is present by
+ * its bit in `sections` and by nothing else: with the bit set its fields are
+ * checked as that block states (a NULL or empty list is then YUMA_EINVAL);
+ * with the bit clear they must be NULL / 0 (YUMA_EINVAL otherwise). The
+ * positional entry points differ only in which NULLs they read as "absent":
+ * each states its mask beside its prototype. A schedule has no bit: it is
+ * present when sched_dev != NULL or K != 0.
+ *
+ * Refusals, all before the first launch and without a HIP call, alike from
+ * yuma_run_request and yuma_graph_create_request (the same code and
+ * yuma_last_error text, before the capture opens): a NULL request; struct_size
+ * != sizeof(yuma_request_t); an unknown section bit; a non-zero reserved word;
+ * the options (as yuma_run_opts); a field of an absent section given (all
+ * YUMA_EINVAL); [the graph handle]; then sizes, NULL params / W / S / out /
+ * workspace, the schedule, and each present section's refusals in the order
+ * its block gives, the workspace size between the YUMA_EINVAL and the
+ * YUMA_EUNSUPPORTED ones. The workspace is yuma_workspace_bytes_request.
+ * A later library version appends fields in place of reserved words and keeps
+ * the size; a library refuses a record of any other size.
+ * ---------------------------------------------------------------------- */
+enum yuma_request_sections {
+  YUMA_REQ_WATCH = 1,      /* watch_dev, n_watch, B_watch          */
+  YUMA_REQ_MOVE = 2,       /* B_move                               */
+  YUMA_REQ_ROWS = 4,       /* rows_dev, n_rows, B_rows             */
+  YUMA_REQ_ROWSTAT = 8,    /* B_rowstat                            */
+  YUMA_REQ_RESETS = 16,    /* events_dev, n_events                 */
+  YUMA_REQ_ROW_EVENTS = 32 /* row_events_dev, n_row_events         */
+};
+typedef struct yuma_request {
+  uint32_t struct_size;    /* sizeof(yuma_request_t)                                */
+  uint32_t sections;       /* yuma_request_sections                                 */
+  int32_t variant;         /* yuma_variant                                          */
+  int32_t N, E;            /* scenarios, epochs                                     */
+  int32_t K;               /* stored slices under a schedule, else 0                */
+  int32_t V, M;            /* validators, miners                                    */
+  const yuma_params_t* params_dev; /* [N], device memory                            */
+  const void* W;           /* [E or K][N][V][M] fp32 (uint16: YUMA_RUN_W_U16)       */
+  const float* S;          /* [E or K][N][V]                                        */
+  const int32_t* sched_dev;/* [E] slice per epoch, or NULL: no schedule             */
+  const float* B_init;     /* [N][V][M] or NULL                                     */
+  const float* Wprev_init; /* Yuma2: [N][V][M] or NULL                              */
+  const yuma_outputs_t* out;
+  void* workspace;
+  size_t workspace_bytes;
+  const yuma_run_options_t* opts; /* NULL: every default                            */
+  const int32_t* watch_dev;/* YUMA_REQ_WATCH: [n_watch] miner columns               */
+  float* B_watch;          /*   [n_hist][N][V][n_watch]                             */
+  float* B_move;           /* YUMA_REQ_MOVE: [E][N][2]                              */
+  const int32_t* rows_dev; /* YUMA_REQ_ROWS: [n_rows] validator rows                */
+  float* B_rows;           /*   [n_hist][N][n_rows][M]                              */
+  float* B_rowstat;        /* YUMA_REQ_ROWSTAT: [E][N][V][3]                        */
+  const yuma_reset_event_t* events_dev;   /* YUMA_REQ_RESETS: [n_events]            */
+  const yuma_row_event_t* row_events_dev; /* YUMA_REQ_ROW_EVENTS: [n_row_events]    */
+  int32_t chunk_epochs;    /* epochs per phase-1 batch (0 = engine default)         */
+  int32_t n_watch, n_rows, n_events, n_row_events;
+  int32_t reserved[15];    /* must be 0                                             */
+} yuma_request_t;          /* 256 bytes */
+/* stream: a hipStream_t, NULL = default stream. phase_ms: NULL, or per-phase
+ * device time as yuma_run_profiled (blocks). */
+int yuma_run_request(const yuma_request_t* request, void* stream, float* phase_ms);
+/* Bytes of workspace the request needs. Reads the sizes, K, `sections` and
+ * whether out->Tv is requested (out may be NULL: not requested); equals the
+ * yuma_workspace_bytes* function of the same shape. 0 for a NULL request, a
+ * wrong struct_size, a non-positive size or K < 0. */
+size_t yuma_workspace_bytes_request(const yuma_request_t* request);
 
 /* ------------------------------------------------------------------------
  * Which bond scan a call reaches. Host only, needs no GPU and makes no HIP
@@ -821,6 +895,8 @@ int yuma_graph_create_events(yuma_graph_t* graph, int variant, const yuma_params
                              const yuma_reset_event_t* events_dev, int n_events,
                              const yuma_row_event_t* row_events_dev, int n_row_events, void* workspace,
                              size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts);
+/* The graph of a request: what every yuma_graph_create* above calls with its run twin's record. */
+int yuma_graph_create_request(yuma_graph_t* graph, const yuma_request_t* request);
 /* Replay on `stream` (stream-ordered, no host synchronisation). */
 int yuma_graph_launch(yuma_graph_t graph, void* stream);
 /* Kernel nodes in the captured graph (diagnostics / tests). */

@@ -2,6 +2,9 @@
 # A/B engine builds: tools/ab_lib.sh lib1.so lib2.so ... [-- extra bench.py args]
 # One bench line per library (YUMA_HIP_LIB), printed as value, ms/step, phase ms;
 # logs under $OUT (default bench_out/).
+# Every library runs under this tree's engine.py, which needs yuma_run_request: a library built from sources
+# older than the request record raises EngineUnavailable. A/B such a parent with its own tree's bench.py and
+# engine.py (python <parent tree>/bench.py ...), alternating the two commands.
 set -u
 OUT=${OUT:-bench_out}
 mkdir -p $OUT

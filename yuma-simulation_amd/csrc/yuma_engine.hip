@@ -6916,55 +6916,17 @@ void launch_finalize(hipStream_t st, long long ns, const float* dsrc, const Work
               out->Tv, dpl, tiles);
 }
 
-// One run as its entry point received it, the yuma_run_options_t resolved
-// (read_opts): every run and graph entry point fills one for run_direct / graph_create_impl.
-struct RunReq {
-  int variant;
-  const yuma_params_t* prm;
-  int N, E, V, M;
-  const void* W;  // fp32, or uint16 under w_u16: element w is the weight (float)w
-  const float *S, *B_init, *Wprev_init;
-  const yuma_outputs_t* out;
-  void* workspace;
-  size_t ws_bytes;
-  int chunk;
+// One run: the public record as its entry point received it (every positional entry point fills one:
+// include/yuma_hip.h documents the fields), and what read_request resolves from it.
+struct RunReq : yuma_request_t {
   void* stream;
   float* phase_ms;  // [YUMA_NUM_PHASES] of a profiled run, or nullptr
-  int wsh = 0, w_u16 = 0, hist_bf16 = 0;  // YUMA_RUN_SHARED_INPUTS / _W_U16 / _HIST_BF16
+  // the options (read_opts): YUMA_RUN_SHARED_INPUTS / _W_U16 / _HIST_BF16 and the history stride
+  int wsh = 0, w_u16 = 0, hist_bf16 = 0;
   int hist_stride = 1, hist_first = 0;
-  // yuma_run_sched: W is [K][N][V][M], S [K][N][V]; epoch t reads stored slice sched[t] ([E], device memory)
-  const int32_t* sched = nullptr;
-  int K = 0;
-  // yuma_run_watch (has_watch): the watched columns watch[n_watch] (device memory) and their history
-  // B_watch [n_hist][N][V][n_watch]
-  int has_watch = 0;
-  const int32_t* watch = nullptr;
-  int n_watch = 0;
-  float* B_watch = nullptr;
-  // yuma_run_move (has_move): the per-epoch bond movement B_move [E][N][2]; its watch list may be empty
-  // (n_watch = 0 with NULL watch / B_watch: has_watch stays 0)
-  int has_move = 0;
-  float* B_move = nullptr;
-  // yuma_run_rows (has_rows): the watched validator rows rows[n_rows] (device memory) and their history
-  // B_rows [n_hist][N][n_rows][M]; its watch list may be empty and its B_move NULL (has_move stays 0)
-  int has_rows = 0;
-  const int32_t* rows = nullptr;
-  int n_rows = 0;
-  float* B_rows = nullptr;
-  // yuma_run_resets (has_resets): the events events[n_events] (device memory); n_events = 0 with a NULL list
-  // leaves has_resets 0, the run yuma_run_opts makes
-  int has_resets = 0;
-  const yuma_reset_event_t* events = nullptr;
-  int n_events = 0;
-  // yuma_run_events (has_rowev, which sets has_resets): the row events row_events[n_row_events] (device memory);
-  // n_row_events = 0 with a NULL list leaves has_rowev 0, the run yuma_run_resets makes
-  int has_rowev = 0;
-  const yuma_row_event_t* row_events = nullptr;
-  int n_row_events = 0;
-  // yuma_run_rowstat (has_rowstat): the per-validator bond summary B_rowstat [E][N][V][3]; its watch and row
-  // lists may be empty (has_watch / has_rows stay 0)
-  int has_rowstat = 0;
-  float* B_rowstat = nullptr;
+  // the sections, one per YUMA_REQ_* bit; has_rowev sets has_resets: a run with row events takes the scan with
+  // both tables, on an all-zero column table where it has no column events
+  int has_watch = 0, has_move = 0, has_rows = 0, has_rowstat = 0, has_resets = 0, has_rowev = 0;
 };
 
 // The history countdown (BondArgs::hnext) of the chunk from epoch A.t0 of the
@@ -7038,6 +7000,11 @@ int check_native(const RunReq& q, bool vec, bool sched, int K) {
                   "matrices 16-byte aligned");
   }
   if (q.has_resets) {
+    // what the RL / RW forms have never run beside (no positional entry point takes both; yuma_request_t can say it)
+    if (sched || q.has_watch || q.has_move || q.has_rows || q.has_rowstat)
+      return fail(YUMA_EUNSUPPORTED,
+                  "reset events do not combine with an input schedule, a watch list, B_move, a row list or the row "
+                  "summary: cut the run at the event epochs");
     const int f = (wsh ? YUMA_RUN_SHARED_INPUTS : 0) | (q.w_u16 ? YUMA_RUN_W_U16 : 0) | (q.hist_bf16 ? YUMA_RUN_HIST_BF16 : 0);
     if (!resets_native(variant, N, E, V, M, out, f))
       return fail(YUMA_EUNSUPPORTED,
@@ -7077,7 +7044,7 @@ int check_native(const RunReq& q, bool vec, bool sched, int K) {
                 variant, V, wsh);
   if (q.has_rowstat) {
     // what the RS forms are not instantiated with, then the predicate, then the alignment
-    if (sched || q.has_move || q.has_resets)
+    if (sched || q.has_move)  // (reset events beside it: refused above)
       return fail(YUMA_EUNSUPPORTED,
                   "the row summary does not combine with an input schedule, B_move or reset events: run the fp32 "
                   "history and reduce it");
@@ -7135,6 +7102,38 @@ RunReq size_req(int variant, int N, int E, int V, int M, const yuma_outputs_t* o
   return q;
 }
 
+// Bytes of workspace the run q needs, and p's carving of q.workspace (NULL: sizes only): the E-epoch workspace
+// (full: with validator_trust's partial sums), behind it the staging set of a schedule's K stored slices
+// (K > 0: run_plan has refused K without a schedule pointer), behind that one of: the reset table and the row
+// table of row events; the reset table; the row summary's I = 1 partials (check_native refuses the summary
+// beside events). run_plan's requirement, and what every yuma_workspace_bytes* returns.
+size_t request_bytes(const RunReq& q, int full, RunPlan* p) {
+  const int N = q.N, E = q.E, V = q.V, M = q.M;
+  char* base = (char*)q.workspace;
+  p->ws = carve(base, q.variant, N, E, V, M, full);
+  p->wk = q.K > 0 ? carve(base ? base + p->ws.bytes : nullptr, q.variant, N, q.K, V, M, 0, true) : Workspace{};
+  const size_t carved = p->ws.bytes + p->wk.bytes;
+  p->rmask_off = q.has_resets ? reset_table_offset(carved) : 0;
+  p->rowmask_off = q.has_rowev ? p->rmask_off + reset_table_bytes(N, E, M) : 0;
+  p->tpart_off = q.has_rowstat ? reset_table_offset(carved) : 0;
+  return q.has_rowev     ? p->rowmask_off + row_table_bytes(N, E, V)
+         : q.has_resets  ? p->rmask_off + reset_table_bytes(N, E, M)
+         : q.has_rowstat ? p->tpart_off + rowstat_part_bytes(N, E, V, M)
+                         : carved;
+}
+
+// request_bytes of sizes and presences alone: the yuma_workspace_bytes* functions (0 on a non-positive size)
+size_t size_bytes(int variant, int N, int E, int K, int V, int M, int full, bool resets, bool rowev, bool rowstat) {
+  if (N < 1 || E < 1 || K < 0 || V < 1 || M < 1) return 0;
+  RunReq q = size_req(variant, N, E, V, M, nullptr);
+  q.K = K;
+  q.has_resets = resets || rowev;
+  q.has_rowev = rowev;
+  q.has_rowstat = rowstat;
+  RunPlan p;
+  return request_bytes(q, full, &p);
+}
+
 // Validate: every refusal of a run, in the order the entry points document,
 // without a HIP call -- so that a capture is refused before it opens
 // (graph_create_impl) by the code and text the direct run returns.
@@ -7143,12 +7142,12 @@ int run_plan(const RunReq& q, RunPlan* p) {
   const yuma_outputs_t* out = q.out;
   if (const int err = check_sizes(variant, N, E, V, M)) return err;
   if (const int err = check_tiles(M)) return err;
-  if (!q.prm || !q.W || !q.S || !out || !q.workspace) return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
-  if (q.sched != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
-  if (q.sched == nullptr && K != 0) return fail(YUMA_EINVAL, "K=%d stored slices without a schedule pointer", K);
+  if (!q.params_dev || !q.W || !q.S || !out || !q.workspace) return fail(YUMA_EINVAL, "null params/W/S/outputs/workspace");
+  if (q.sched_dev != nullptr && K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
+  if (q.sched_dev == nullptr && K != 0) return fail(YUMA_EINVAL, "K=%d stored slices without a schedule pointer", K);
   if (q.has_watch) {
     if (q.n_watch < 1) return fail(YUMA_EINVAL, "n_watch=%d watched columns: at least one is required", q.n_watch);
-    if (q.watch == nullptr || q.B_watch == nullptr) return fail(YUMA_EINVAL, "the watch list or B_watch is NULL");
+    if (q.watch_dev == nullptr || q.B_watch == nullptr) return fail(YUMA_EINVAL, "the watch list or B_watch is NULL");
     // (k_bonds_watch: one wave per block, N blocks-per-scenario blocks)
     if (((long long)V * q.n_watch + yk::kWatchBS - 1) / yk::kWatchBS * N > INT_MAX)
       return fail(YUMA_EINVAL, "n_watch=%d: N V n_watch elements exceed the watch kernel's grid", q.n_watch);
@@ -7156,38 +7155,27 @@ int run_plan(const RunReq& q, RunPlan* p) {
   if (q.has_move && q.B_move == nullptr) return fail(YUMA_EINVAL, "B_move is NULL");
   if (q.has_rows) {
     if (q.n_rows < 1) return fail(YUMA_EINVAL, "n_rows=%d watched rows: at least one is required", q.n_rows);
-    if (q.rows == nullptr || q.B_rows == nullptr) return fail(YUMA_EINVAL, "the row list or B_rows is NULL");
+    if (q.rows_dev == nullptr || q.B_rows == nullptr) return fail(YUMA_EINVAL, "the row list or B_rows is NULL");
     // (k_bonds_rows: one wave per block, N n_rows blocks-per-row blocks; the scalar form has the most)
     if (rows_bpr(M, 1) * q.n_rows * N > INT_MAX)
       return fail(YUMA_EINVAL, "n_rows=%d: N n_rows M elements exceed the row kernel's grid", q.n_rows);
   }
   if (q.has_rowstat && q.B_rowstat == nullptr) return fail(YUMA_EINVAL, "B_rowstat is NULL");
   if (q.n_events < 0) return fail(YUMA_EINVAL, "n_events=%d must not be negative", q.n_events);
-  if (q.n_events > 0 && q.events == nullptr) return fail(YUMA_EINVAL, "n_events=%d with a NULL event list", q.n_events);
+  if (q.n_events > 0 && q.events_dev == nullptr) return fail(YUMA_EINVAL, "n_events=%d with a NULL event list", q.n_events);
   if (q.n_row_events < 0) return fail(YUMA_EINVAL, "n_row_events=%d must not be negative", q.n_row_events);
-  if (q.n_row_events > 0 && q.row_events == nullptr)
+  if (q.n_row_events > 0 && q.row_events_dev == nullptr)
     return fail(YUMA_EINVAL, "n_row_events=%d with a NULL row event list", q.n_row_events);
   const int full = out->Tv != nullptr;
   // bisection trip counts above 30 (consensus_precision > 2^30) are not supported;
   // params live in device memory, so the Python marshaller enforces it.
-  p->ws = carve((char*)q.workspace, variant, N, E, V, M, full);
-  p->wk = q.sched ? carve((char*)q.workspace + p->ws.bytes, variant, N, K, V, M, 0, true) : Workspace{};
-  // (reset events: the table behind the carved workspace; they come without a schedule)
-  p->rmask_off = q.has_resets ? reset_table_offset(p->ws.bytes) : 0;
-  p->rowmask_off = q.has_rowev ? p->rmask_off + reset_table_bytes(N, E, M) : 0;
-  // (row summary: the I = 1 partials behind the carved workspace and a schedule's staging set; check_native
-  // refuses it beside a schedule or events)
-  p->tpart_off = q.has_rowstat ? reset_table_offset(p->ws.bytes + p->wk.bytes) : 0;
-  const size_t need = q.has_rowev      ? p->rowmask_off + row_table_bytes(N, E, V)
-                      : q.has_resets ? p->rmask_off + reset_table_bytes(N, E, M)
-                      : q.has_rowstat ? p->tpart_off + rowstat_part_bytes(N, E, V, M)
-                                     : p->ws.bytes + p->wk.bytes;
-  if (need > q.ws_bytes)
-    return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)", q.ws_bytes, need, full);
+  const size_t need = request_bytes(q, full, p);
+  if (need > q.workspace_bytes)
+    return fail(YUMA_EWORKSPACE, "workspace %zu < required %zu bytes (full_outputs=%d)", q.workspace_bytes, need, full);
   p->tiles = (M + yk::kTileM - 1) / yk::kTileM;
   p->rc = row_cfg(V);
   const bool vec = p->vec = vector_form(M, q.W, q.B_init, q.Wprev_init, out, q.hist_bf16 != 0, q.w_u16 ? 2 : 4);
-  return check_native(q, vec, q.sched != nullptr, K);
+  return check_native(q, vec, q.sched_dev != nullptr, K);
 }
 
 // Enqueue the run that run_plan admitted, on q.stream. WT: the element type
@@ -7201,13 +7189,13 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
   constexpr bool U16 = std::is_same_v<WT, uint16_t>;
   static_assert(U16 || std::is_same_v<WT, float>, "weights are fp32 or uint16");
   const int variant = q.variant, N = q.N, E = q.E, V = q.V, M = q.M, K = q.K, wsh = q.wsh;
-  const int tiles = plan.tiles, chunk0 = q.chunk;
+  const int tiles = plan.tiles, chunk0 = q.chunk_epochs;
   const RowCfg rc = plan.rc;
-  const yuma_params_t* prm = q.prm;
+  const yuma_params_t* prm = q.params_dev;
   const WT* W = static_cast<const WT*>(q.W);
   const float *S = q.S, *B_init = q.B_init, *Wprev_init = q.Wprev_init;
   const yuma_outputs_t* out = q.out;
-  const int32_t* sched = q.sched;
+  const int32_t* sched = q.sched_dev;
   float* phase_ms = q.phase_ms;
   const Workspace &ws = plan.ws, &wk = plan.wk;
   const bool vec = plan.vec;
@@ -7377,10 +7365,10 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     const long long ns = (long long)(c1 - c0) * N;
     if (sched == nullptr) phase1(ws, buf, c0, c1);
     if (q.has_resets && q.n_events > 0)  // (counted under YUMA_PHASE_INCENTIVE, the phase it follows)
-      YK_LAUNCH(yk::k_reset_events, ((long long)q.n_events + 255) / 256, 256, st, q.events, q.n_events, buf.C,
+      YK_LAUNCH(yk::k_reset_events, ((long long)q.n_events + 255) / 256, 256, st, q.events_dev, q.n_events, buf.C,
                 reinterpret_cast<unsigned*>(rmask), N, E, M, c0, c1, B_init != nullptr ? 1 : 0);
     if (q.has_rowev && q.n_row_events > 0)
-      YK_LAUNCH(yk::k_row_events, ((long long)q.n_row_events + 255) / 256, 256, st, q.row_events, q.n_row_events,
+      YK_LAUNCH(yk::k_row_events, ((long long)q.n_row_events + 255) / 256, 256, st, q.row_events_dev, q.n_row_events,
                 rowmask, N, E, V, c0, c1, B_init != nullptr ? 1 : 0);
 
     // (A.W: the scan is launched for WT)
@@ -7395,9 +7383,9 @@ int run_impl(const RunReq& q, const RunPlan& plan) {
     hist_countdown(q, &A);
     tm.mark(YUMA_PHASE_BONDS);
     if (q.has_watch)  // (Yuma 3 / Yuma 4: run_plan) the state before epoch c0 is still in A.Bstate
-      launch_watch<WT>(st, variant, A, q.watch, q.n_watch, q.B_watch, sched, K);
+      launch_watch<WT>(st, variant, A, q.watch_dev, q.n_watch, q.B_watch, sched, K);
     if (q.has_rows)  // (likewise)
-      launch_rows<WT>(st, variant, A, q.rows, q.n_rows, q.B_rows, sched, K);
+      launch_rows<WT>(st, variant, A, q.rows_dev, q.n_rows, q.B_rows, sched, K);
     const ScanPlan scan = plan_scan(scan_key(q, vec, sched != nullptr, true, yk::hist_strided(A)));
     launch_scan(st, scan, A, sched, K, q.B_move, rmask, rowmask, q.B_rowstat, tpart);
     const int ptiles = scan.ptiles;
@@ -7827,84 +7815,104 @@ int read_opts(const yuma_run_options_t* o, RunReq* q) {
   return YUMA_OK;
 }
 
-// What yuma_run_sched and yuma_graph_create_sched refuse alike, first; then the schedule is the request's.
-int read_sched(const int32_t* sched_dev, int K, RunReq* q) {
+// What yuma_run_sched and yuma_graph_create_sched refuse alike, first: their schedule is mandatory.
+int check_sched(const int32_t* sched_dev, int K) {
   if (K < 1) return fail(YUMA_EINVAL, "K=%d stored slices: at least one is required", K);
   if (sched_dev == nullptr) return fail(YUMA_EINVAL, "the schedule pointer is NULL");
-  q->sched = sched_dev;
-  q->K = K;
   return YUMA_OK;
 }
 
-// yuma_run_watch / yuma_graph_create_watch: the schedule (none: NULL and K = 0) and the watch list as given;
-// run_plan refuses what is wrong with them.
-void read_watch(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, RunReq* q) {
-  q->sched = sched_dev;
-  q->K = K;
-  q->has_watch = 1;
-  q->watch = watch_dev;
-  q->n_watch = n_watch;
-  q->B_watch = B_watch;
+static_assert(sizeof(yuma_request_t) == 256, "yuma_request_t: 8 ints, 18 pointer-sized words, 20 ints");
+constexpr uint32_t kReqSections = YUMA_REQ_WATCH | YUMA_REQ_MOVE | YUMA_REQ_ROWS | YUMA_REQ_ROWSTAT |
+                                  YUMA_REQ_RESETS | YUMA_REQ_ROW_EVENTS;
+
+// yuma_request_t checked and resolved into the request: the record itself, then its options (read_opts), then
+// every section's fields against its bit. A section is present by its bit alone (has_*); run_plan refuses what
+// is wrong with a present section's fields. sched_required: yuma_run_sched's own early check.
+int read_request(const yuma_request_t* r, void* stream, float* phase_ms, bool sched_required, RunReq* q) {
+  if (r == nullptr) return fail(YUMA_EINVAL, "the request is NULL");
+  if (r->struct_size != sizeof(yuma_request_t))
+    return fail(YUMA_EINVAL, "yuma_request_t.struct_size=%u: this library's record has %zu bytes", r->struct_size,
+                sizeof(yuma_request_t));
+  if (r->sections & ~kReqSections) return fail(YUMA_EINVAL, "unknown request sections 0x%x", r->sections);
+  for (int w : r->reserved)
+    if (w != 0) return fail(YUMA_EINVAL, "yuma_request_t.reserved must be 0");
+  static_cast<yuma_request_t&>(*q) = *r;
+  q->stream = stream;
+  q->phase_ms = phase_ms;
+  if (const int err = read_opts(r->opts, q)) return err;
+  if (sched_required)
+    if (const int err = check_sched(r->sched_dev, r->K)) return err;
+  const auto has = [r](uint32_t bit) { return (r->sections & bit) != 0 ? 1 : 0; };
+  if (!has(YUMA_REQ_WATCH) && (r->watch_dev != nullptr || r->n_watch != 0 || r->B_watch != nullptr))
+    return fail(YUMA_EINVAL, "watch_dev, n_watch or B_watch given without YUMA_REQ_WATCH");
+  if (!has(YUMA_REQ_MOVE) && r->B_move != nullptr) return fail(YUMA_EINVAL, "B_move given without YUMA_REQ_MOVE");
+  if (!has(YUMA_REQ_ROWS) && (r->rows_dev != nullptr || r->n_rows != 0 || r->B_rows != nullptr))
+    return fail(YUMA_EINVAL, "rows_dev, n_rows or B_rows given without YUMA_REQ_ROWS");
+  if (!has(YUMA_REQ_ROWSTAT) && r->B_rowstat != nullptr)
+    return fail(YUMA_EINVAL, "B_rowstat given without YUMA_REQ_ROWSTAT");
+  if (!has(YUMA_REQ_RESETS) && (r->events_dev != nullptr || r->n_events != 0))
+    return fail(YUMA_EINVAL, "events_dev or n_events given without YUMA_REQ_RESETS");
+  if (!has(YUMA_REQ_ROW_EVENTS) && (r->row_events_dev != nullptr || r->n_row_events != 0))
+    return fail(YUMA_EINVAL, "row_events_dev or n_row_events given without YUMA_REQ_ROW_EVENTS");
+  q->has_watch = has(YUMA_REQ_WATCH);
+  q->has_move = has(YUMA_REQ_MOVE);
+  q->has_rows = has(YUMA_REQ_ROWS);
+  q->has_rowstat = has(YUMA_REQ_ROWSTAT);
+  q->has_resets = has(YUMA_REQ_RESETS | YUMA_REQ_ROW_EVENTS);
+  q->has_rowev = has(YUMA_REQ_ROW_EVENTS);
+  return YUMA_OK;
 }
 
-// yuma_run_move / yuma_graph_create_move: as read_watch, but n_watch = 0 with NULL watch_dev and B_watch is
-// "no watch list"; and the movement output as given (run_plan refuses a NULL one).
-void read_move(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
-               RunReq* q) {
-  read_watch(sched_dev, K, watch_dev, n_watch, B_watch, q);
-  if (n_watch == 0 && watch_dev == nullptr && B_watch == nullptr) q->has_watch = 0;
-  q->has_move = 1;
-  q->B_move = B_move;
-}
-
-// yuma_run_rows / yuma_graph_create_rows: as read_move, but a NULL B_move is "no movement output"; and the row
-// list as given (run_plan refuses what is wrong with it).
-void read_rows(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
-               const int32_t* rows_dev, int n_rows, float* B_rows, RunReq* q) {
-  read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, q);
-  if (B_move == nullptr) q->has_move = 0;
-  q->has_rows = 1;
-  q->rows = rows_dev;
-  q->n_rows = n_rows;
-  q->B_rows = B_rows;
-}
-
-// yuma_run_rowstat / yuma_graph_create_rowstat: as read_rows, but n_rows = 0 with NULL rows_dev and B_rows is
-// "no row list"; and the summary output as given (run_plan refuses a NULL one; check_native a schedule or a
-// B_move beside it).
-void read_rowstat(const int32_t* sched_dev, int K, const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
-                  const int32_t* rows_dev, int n_rows, float* B_rows, float* B_rowstat, RunReq* q) {
-  read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, q);
-  if (n_rows == 0 && rows_dev == nullptr && B_rows == nullptr) q->has_rows = 0;
-  q->has_rowstat = 1;
-  q->B_rowstat = B_rowstat;
-}
-
-// yuma_run_resets / yuma_graph_create_resets: the event list as given (run_plan refuses what is wrong with it);
-// n_events = 0 with a NULL list is "no events", the run of yuma_run_opts.
-void read_resets(const yuma_reset_event_t* events_dev, int n_events, RunReq* q) {
-  q->has_resets = (n_events != 0 || events_dev != nullptr) ? 1 : 0;
-  q->events = events_dev;
-  q->n_events = n_events;
-}
-
-// yuma_run_events / yuma_graph_create_events: the row event list as given beside the column list (run_plan refuses
-// what is wrong with either); n_row_events = 0 with a NULL list is "no row events", the run of yuma_run_resets. A
-// run with row events takes the scan with both tables, on an all-zero column table where it has no column events.
-void read_events(const yuma_reset_event_t* events_dev, int n_events, const yuma_row_event_t* row_events_dev,
-                 int n_row_events, RunReq* q) {
-  read_resets(events_dev, n_events, q);
-  q->has_rowev = (n_row_events != 0 || row_events_dev != nullptr) ? 1 : 0;
-  if (q->has_rowev) q->has_resets = 1;
-  q->row_events = row_events_dev;
-  q->n_row_events = n_row_events;
-}
-
-// A direct run: validate, then enqueue on the caller's stream, in the weight type the request names.
-int run_direct(const RunReq& q) {
+// A direct run of a public record: resolve, validate, then enqueue on the caller's stream, in the weight type
+// the request names. sched_required: see read_request.
+int run_request(const yuma_request_t& r, void* stream, float* phase_ms, bool sched_required = false) {
+  RunReq q{};
   RunPlan p;
+  if (const int err = read_request(&r, stream, phase_ms, sched_required, &q)) return err;
   if (const int err = run_plan(q, &p)) return err;
   return q.w_u16 ? run_impl<uint16_t>(q, p) : run_impl<float>(q, p);
+}
+
+// The record of a positional entry point: what every rung passes (no schedule: NULL and K = 0), no section.
+yuma_request_t request_of(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
+                          const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
+                          const float* Wprev_init, const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
+                          int chunk_epochs, const yuma_run_options_t* opts) {
+  yuma_request_t r{sizeof(yuma_request_t), 0, variant, N, E, K, V, M, params_dev, W, S, sched_dev, B_init, Wprev_init,
+                   out, workspace, workspace_bytes, opts};  // (the record's leading fields, in its order)
+  r.chunk_epochs = chunk_epochs;
+  return r;
+}
+
+// A rung's optional list, (NULL, 0, NULL) or (NULL, 0), is present when any of its arguments is given
+uint32_t given(uint32_t bit, const void* list, int n, const void* hist = nullptr) {
+  return (list != nullptr || n != 0 || hist != nullptr) ? bit : 0;
+}
+
+// The sections of the watch ... rowstat rungs: the mask as the rung reads its NULLs, and the fields as passed
+void set_lists(yuma_request_t* r, uint32_t sections, const int32_t* watch_dev, int n_watch, float* B_watch,
+               float* B_move = nullptr, const int32_t* rows_dev = nullptr, int n_rows = 0, float* B_rows = nullptr,
+               float* B_rowstat = nullptr) {
+  r->sections = sections;
+  r->watch_dev = watch_dev;
+  r->n_watch = n_watch;
+  r->B_watch = B_watch;
+  r->B_move = B_move;
+  r->rows_dev = rows_dev;
+  r->n_rows = n_rows;
+  r->B_rows = B_rows;
+  r->B_rowstat = B_rowstat;
+}
+
+// The sections of the resets and events rungs: either list is present when given
+void set_events(yuma_request_t* r, const yuma_reset_event_t* events_dev, int n_events,
+                const yuma_row_event_t* row_events_dev = nullptr, int n_row_events = 0) {
+  r->sections = given(YUMA_REQ_RESETS, events_dev, n_events) | given(YUMA_REQ_ROW_EVENTS, row_events_dev, n_row_events);
+  r->events_dev = events_dev;
+  r->n_events = n_events;
+  r->row_events_dev = row_events_dev;
+  r->n_row_events = n_row_events;
 }
 }  // namespace
 
@@ -7914,8 +7922,14 @@ struct yuma_graph {
 };
 
 namespace {
-// The capture behind every yuma_graph_create*: the request validated as a
-// direct run validates it, then enqueued on a capture stream of its own.
+// The capture behind every yuma_graph_create*: the record resolved as a direct run resolves it, then the handle,
+// then the request validated as a direct run validates it, then enqueued on a capture stream of its own.
+int graph_create_impl(yuma_graph_t* graph, RunReq q);
+int graph_request(yuma_graph_t* graph, const yuma_request_t* r, bool sched_required = false) {
+  RunReq q{};
+  if (const int err = read_request(r, nullptr, nullptr, sched_required, &q)) return err;
+  return graph_create_impl(graph, q);
+}
 int graph_create_impl(yuma_graph_t* graph, RunReq q) {
   if (graph == nullptr) return fail(YUMA_EINVAL, "graph handle pointer is NULL");
   *graph = nullptr;
@@ -7953,54 +7967,49 @@ int graph_create_impl(yuma_graph_t* graph, RunReq q) {
 extern "C" {
 
 size_t yuma_workspace_bytes(int variant, int N, int E, int V, int M, int full_outputs) {
-  if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
-  return carve(nullptr, variant, N, E, V, M, full_outputs).bytes;
+  return size_bytes(variant, N, E, 0, V, M, full_outputs, false, false, false);
 }
 
 int yuma_run(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
              const float* W, const float* S, const float* B_init, const float* Wprev_init,
              const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
              int chunk_epochs, void* stream) {
-  return run_direct(RunReq{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                           workspace_bytes, chunk_epochs, stream, nullptr});
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, nullptr);
+  return run_request(r, stream, nullptr);
 }
 
 int yuma_run_ex(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                 const float* W, const float* S, const float* B_init, const float* Wprev_init,
                 const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                 int chunk_epochs, int flags, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
   const yuma_run_options_t o{flags};
-  if (const int err = read_opts(&o, &q)) return err;
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, &o);
+  return run_request(r, stream, phase_ms);
 }
 
 int yuma_run_opts(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
                   const float* W, const float* S, const float* B_init, const float* Wprev_init,
                   const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                   int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  return run_request(r, stream, phase_ms);
 }
 
 size_t yuma_workspace_bytes_sched(int variant, int N, int E, int K, int V, int M, int full_outputs) {
-  if (N < 1 || E < 1 || K < 1 || V < 1 || M < 1) return 0;
-  return carve(nullptr, variant, N, E, V, M, full_outputs).bytes +
-         carve(nullptr, variant, N, K, V, M, 0, true).bytes;
+  if (K < 1) return 0;
+  return size_bytes(variant, N, E, K, V, M, full_outputs, false, false, false);
 }
 
 int yuma_run_sched(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
                    const float* W, const float* S, const int32_t* sched_dev, const float* B_init,
                    const float* Wprev_init, const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                    int chunk_epochs, const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  if (const int err = read_sched(sched_dev, K, &q)) return err;
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  return run_request(r, stream, phase_ms, true);
 }
 
 int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
@@ -8008,11 +8017,10 @@ int yuma_run_watch(int variant, const yuma_params_t* params_dev, int N, int E, i
                    const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
                    float* B_watch, void* workspace, size_t workspace_bytes, int chunk_epochs,
                    const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_watch(sched_dev, K, watch_dev, n_watch, B_watch, &q);
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_WATCH, watch_dev, n_watch, B_watch);
+  return run_request(r, stream, phase_ms);
 }
 
 int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
@@ -8020,11 +8028,10 @@ int yuma_run_move(int variant, const yuma_params_t* params_dev, int N, int E, in
                   const float* Wprev_init, const yuma_outputs_t* out, const int32_t* watch_dev, int n_watch,
                   float* B_watch, float* B_move, void* workspace, size_t workspace_bytes, int chunk_epochs,
                   const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, &q);
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_MOVE | given(YUMA_REQ_WATCH, watch_dev, n_watch, B_watch), watch_dev, n_watch, B_watch, B_move);
+  return run_request(r, stream, phase_ms);
 }
 
 int yuma_run_rows(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
@@ -8033,16 +8040,15 @@ int yuma_run_rows(int variant, const yuma_params_t* params_dev, int N, int E, in
                   float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows, float* B_rows, void* workspace,
                   size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts, void* stream,
                   float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, &q);
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_ROWS | given(YUMA_REQ_WATCH, watch_dev, n_watch, B_watch) | (B_move ? YUMA_REQ_MOVE : 0),
+            watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows);
+  return run_request(r, stream, phase_ms);
 }
 
 size_t yuma_workspace_bytes_rowstat(int variant, int N, int E, int V, int M, int full_outputs) {
-  if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
-  return reset_table_offset(carve(nullptr, variant, N, E, V, M, full_outputs).bytes) + rowstat_part_bytes(N, E, V, M);
+  return size_bytes(variant, N, E, 0, V, M, full_outputs, false, false, true);
 }
 
 int yuma_run_rowstat(int variant, const yuma_params_t* params_dev, int N, int E, int K, int V, int M,
@@ -8051,11 +8057,12 @@ int yuma_run_rowstat(int variant, const yuma_params_t* params_dev, int N, int E,
                      float* B_watch, float* B_move, const int32_t* rows_dev, int n_rows, float* B_rows,
                      float* B_rowstat, void* workspace, size_t workspace_bytes, int chunk_epochs,
                      const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_rowstat(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, B_rowstat, &q);
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_ROWSTAT | given(YUMA_REQ_WATCH, watch_dev, n_watch, B_watch) | (B_move ? YUMA_REQ_MOVE : 0) |
+                    given(YUMA_REQ_ROWS, rows_dev, n_rows, B_rows),
+            watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, B_rowstat);
+  return run_request(r, stream, phase_ms);
 }
 
 int yuma_rowstat_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
@@ -8063,8 +8070,7 @@ int yuma_rowstat_native(int variant, int N, int E, int V, int M, const yuma_outp
 }
 
 size_t yuma_workspace_bytes_resets(int variant, int N, int E, int V, int M, int full_outputs) {
-  if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
-  return reset_table_offset(carve(nullptr, variant, N, E, V, M, full_outputs).bytes) + reset_table_bytes(N, E, M);
+  return size_bytes(variant, N, E, 0, V, M, full_outputs, true, false, false);
 }
 
 int yuma_run_resets(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
@@ -8072,11 +8078,10 @@ int yuma_run_resets(int variant, const yuma_params_t* params_dev, int N, int E, 
                     const yuma_outputs_t* out, const yuma_reset_event_t* events_dev, int n_events,
                     void* workspace, size_t workspace_bytes, int chunk_epochs,
                     const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_resets(events_dev, n_events, &q);
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_events(&r, events_dev, n_events);
+  return run_request(r, stream, phase_ms);
 }
 
 int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outputs_t* out, int flags) {
@@ -8084,8 +8089,7 @@ int yuma_resets_native(int variant, int N, int E, int V, int M, const yuma_outpu
 }
 
 size_t yuma_workspace_bytes_events(int variant, int N, int E, int V, int M, int full_outputs) {
-  if (N < 1 || E < 1 || V < 1 || M < 1) return 0;
-  return yuma_workspace_bytes_resets(variant, N, E, V, M, full_outputs) + row_table_bytes(N, E, V);
+  return size_bytes(variant, N, E, 0, V, M, full_outputs, true, true, false);
 }
 
 int yuma_run_events(int variant, const yuma_params_t* params_dev, int N, int E, int V, int M,
@@ -8094,11 +8098,10 @@ int yuma_run_events(int variant, const yuma_params_t* params_dev, int N, int E, 
                     const yuma_row_event_t* row_events_dev, int n_row_events,
                     void* workspace, size_t workspace_bytes, int chunk_epochs,
                     const yuma_run_options_t* opts, void* stream, float* phase_ms) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, stream, phase_ms};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_events(events_dev, n_events, row_events_dev, n_row_events, &q);
-  return run_direct(q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_events(&r, events_dev, n_events, row_events_dev, n_row_events);
+  return run_request(r, stream, phase_ms);
 }
 
 // (the native set of row events is that of the column events: the same scan shapes)
@@ -8166,16 +8169,18 @@ int yuma_run_profiled(int variant, const yuma_params_t* params_dev, int N, int E
                       const float* Wprev_init, const yuma_outputs_t* out, void* workspace,
                       size_t workspace_bytes, int chunk_epochs, void* stream, float* phase_ms) {
   if (phase_ms == nullptr) return fail(YUMA_EINVAL, "phase_ms is required");
-  return run_direct(RunReq{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace,
-                           workspace_bytes, chunk_epochs, stream, phase_ms});
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, nullptr);
+  return run_request(r, stream, phase_ms);
 }
 
 int yuma_epoch(int variant, const yuma_params_t* params_dev, int N, int V, int M,
                const float* W, const float* W_prev, const float* S, const float* B_old,
                const yuma_outputs_t* out, void* workspace, size_t workspace_bytes,
                void* stream) {
-  return run_direct(RunReq{variant, params_dev, N, 1, V, M, W, S, B_old, W_prev, out, workspace,
-                           workspace_bytes, 1, stream, nullptr});
+  yuma_request_t r = request_of(variant, params_dev, N, 1, 0, V, M, W, S, nullptr, B_old, W_prev, out, workspace,
+                                workspace_bytes, 1, nullptr);
+  return run_request(r, stream, nullptr);
 }
 
 int yuma_synth_weights(uint64_t seed, int E, int N, int V, int M, int t0, float* W,
@@ -8205,10 +8210,9 @@ int yuma_graph_create_opts(yuma_graph_t* graph, int variant, const yuma_params_t
                            const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                            void* workspace, size_t workspace_bytes, int chunk_epochs,
                            const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
@@ -8216,11 +8220,9 @@ int yuma_graph_create_sched(yuma_graph_t* graph, int variant, const yuma_params_
                             const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                             void* workspace, size_t workspace_bytes, int chunk_epochs,
                             const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  if (const int err = read_sched(sched_dev, K, &q)) return err;
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  return graph_request(graph, &r, true);
 }
 
 int yuma_graph_create_watch(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
@@ -8228,11 +8230,10 @@ int yuma_graph_create_watch(yuma_graph_t* graph, int variant, const yuma_params_
                             const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                             const int32_t* watch_dev, int n_watch, float* B_watch, void* workspace,
                             size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_watch(sched_dev, K, watch_dev, n_watch, B_watch, &q);
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_WATCH, watch_dev, n_watch, B_watch);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
@@ -8240,11 +8241,10 @@ int yuma_graph_create_move(yuma_graph_t* graph, int variant, const yuma_params_t
                            const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                            const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move, void* workspace,
                            size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_move(sched_dev, K, watch_dev, n_watch, B_watch, B_move, &q);
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_MOVE | given(YUMA_REQ_WATCH, watch_dev, n_watch, B_watch), watch_dev, n_watch, B_watch, B_move);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create_rows(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
@@ -8253,11 +8253,11 @@ int yuma_graph_create_rows(yuma_graph_t* graph, int variant, const yuma_params_t
                            const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
                            const int32_t* rows_dev, int n_rows, float* B_rows, void* workspace,
                            size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_rows(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, &q);
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_ROWS | given(YUMA_REQ_WATCH, watch_dev, n_watch, B_watch) | (B_move ? YUMA_REQ_MOVE : 0),
+            watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create_rowstat(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N, int E,
@@ -8266,11 +8266,12 @@ int yuma_graph_create_rowstat(yuma_graph_t* graph, int variant, const yuma_param
                               const int32_t* watch_dev, int n_watch, float* B_watch, float* B_move,
                               const int32_t* rows_dev, int n_rows, float* B_rows, float* B_rowstat, void* workspace,
                               size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_rowstat(sched_dev, K, watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, B_rowstat, &q);
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, K, V, M, W, S, sched_dev, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_lists(&r, YUMA_REQ_ROWSTAT | given(YUMA_REQ_WATCH, watch_dev, n_watch, B_watch) | (B_move ? YUMA_REQ_MOVE : 0) |
+                    given(YUMA_REQ_ROWS, rows_dev, n_rows, B_rows),
+            watch_dev, n_watch, B_watch, B_move, rows_dev, n_rows, B_rows, B_rowstat);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
@@ -8278,11 +8279,10 @@ int yuma_graph_create_resets(yuma_graph_t* graph, int variant, const yuma_params
                              const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                              const yuma_reset_event_t* events_dev, int n_events, void* workspace,
                              size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_resets(events_dev, n_events, &q);
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_events(&r, events_dev, n_events);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create_events(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
@@ -8291,30 +8291,45 @@ int yuma_graph_create_events(yuma_graph_t* graph, int variant, const yuma_params
                              const yuma_reset_event_t* events_dev, int n_events,
                              const yuma_row_event_t* row_events_dev, int n_row_events, void* workspace,
                              size_t workspace_bytes, int chunk_epochs, const yuma_run_options_t* opts) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
-  if (const int err = read_opts(opts, &q)) return err;
-  read_events(events_dev, n_events, row_events_dev, n_row_events, &q);
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, opts);
+  set_events(&r, events_dev, n_events, row_events_dev, n_row_events);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create_ex(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
                          int E, int V, int M, const float* W, const float* S,
                          const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                          void* workspace, size_t workspace_bytes, int chunk_epochs, int flags) {
-  RunReq q{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out, workspace, workspace_bytes,
-           chunk_epochs, nullptr, nullptr};
   const yuma_run_options_t o{flags};
-  if (const int err = read_opts(&o, &q)) return err;
-  return graph_create_impl(graph, q);
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, &o);
+  return graph_request(graph, &r);
 }
 
 int yuma_graph_create(yuma_graph_t* graph, int variant, const yuma_params_t* params_dev, int N,
                       int E, int V, int M, const float* W, const float* S,
                       const float* B_init, const float* Wprev_init, const yuma_outputs_t* out,
                       void* workspace, size_t workspace_bytes, int chunk_epochs) {
-  return graph_create_impl(graph, RunReq{variant, params_dev, N, E, V, M, W, S, B_init, Wprev_init, out,
-                                         workspace, workspace_bytes, chunk_epochs, nullptr, nullptr});
+  yuma_request_t r = request_of(variant, params_dev, N, E, 0, V, M, W, S, nullptr, B_init, Wprev_init, out, workspace, workspace_bytes,
+                                chunk_epochs, nullptr);
+  return graph_request(graph, &r);
+}
+
+int yuma_run_request(const yuma_request_t* request, void* stream, float* phase_ms) {
+  if (request == nullptr) return fail(YUMA_EINVAL, "the request is NULL");
+  return run_request(*request, stream, phase_ms);
+}
+
+int yuma_graph_create_request(yuma_graph_t* graph, const yuma_request_t* request) {
+  return graph_request(graph, request);
+}
+
+size_t yuma_workspace_bytes_request(const yuma_request_t* r) {
+  if (r == nullptr || r->struct_size != sizeof(yuma_request_t)) return 0;
+  return size_bytes(r->variant, r->N, r->E, r->K, r->V, r->M, r->out != nullptr && r->out->Tv != nullptr,
+                    (r->sections & YUMA_REQ_RESETS) != 0, (r->sections & YUMA_REQ_ROW_EVENTS) != 0,
+                    (r->sections & YUMA_REQ_ROWSTAT) != 0);
 }
 
 int yuma_graph_launch(yuma_graph_t graph, void* stream) {

@@ -72,6 +72,9 @@ EXPORTED_SYMBOLS = (
     "yuma_run_events",
     "yuma_events_native",
     "yuma_graph_create_events",
+    "yuma_run_request",
+    "yuma_graph_create_request",
+    "yuma_workspace_bytes_request",
     "yuma_scan_plan",
     "yuma_epoch",
     "yuma_synth_weights",
@@ -185,6 +188,25 @@ class YumaRunOptionsC(ctypes.Structure):
 assert ctypes.sizeof(YumaRunOptionsC) == 32, ctypes.sizeof(YumaRunOptionsC)
 
 
+REQ_WATCH, REQ_MOVE, REQ_ROWS, REQ_ROWSTAT, REQ_RESETS, REQ_ROW_EVENTS = 1, 2, 4, 8, 16, 32  # yuma_request_sections
+
+
+class YumaRequestC(ctypes.Structure):
+    """yuma_request_t (include/yuma_hip.h): 256 bytes. A section is present by its REQ_* bit in `sections`."""
+    _fields_ = ([("struct_size", ctypes.c_uint32), ("sections", ctypes.c_uint32)]
+                + [(n, ctypes.c_int32) for n in ("variant", "N", "E", "K", "V", "M")]
+                + [(n, ctypes.c_void_p) for n in ("params_dev", "W", "S", "sched_dev", "B_init", "Wprev_init", "out",
+                                                  "workspace")]
+                + [("workspace_bytes", ctypes.c_size_t)]
+                + [(n, ctypes.c_void_p) for n in ("opts", "watch_dev", "B_watch", "B_move", "rows_dev", "B_rows",
+                                                  "B_rowstat", "events_dev", "row_events_dev")]
+                + [(n, ctypes.c_int32) for n in ("chunk_epochs", "n_watch", "n_rows", "n_events", "n_row_events")]
+                + [("reserved", ctypes.c_int32 * 15)])
+
+
+assert ctypes.sizeof(YumaRequestC) == 256, ctypes.sizeof(YumaRequestC)
+
+
 class YumaShardIOC(ctypes.Structure):
     """yuma_shard_io_t (include/yuma_hip.h): two ints, then device pointers."""
     _fields_ = [("M_total", ctypes.c_int), ("col0", ctypes.c_int)] + [
@@ -245,84 +267,47 @@ def load_library(path: str | None = None):
         lib.yuma_graph_create_ex.restype = i32
         lib.yuma_graph_create_opts.argtypes = lib.yuma_graph_create.argtypes + [vp]
         lib.yuma_graph_create_opts.restype = i32
-        # input schedules: E and K in place of E, the schedule after S
-        if hasattr(lib, "yuma_run_sched"):  # (A/B libraries of older sources lack them)
-            lib.yuma_workspace_bytes_sched.argtypes = [i32, i32, i32, i32, i32, i32, i32]
-            lib.yuma_workspace_bytes_sched.restype = sz
-            lib.yuma_run_sched.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp, vp,
-                                           ctypes.POINTER(ctypes.c_float)]
-            lib.yuma_run_sched.restype = i32
-            lib.yuma_sched_native.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32]
-            lib.yuma_sched_native.restype = i32
-            lib.yuma_graph_create_sched.argtypes = [ctypes.POINTER(vp), i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp,
-                                                    vp, vp, vp, sz, i32, vp]
-            lib.yuma_graph_create_sched.restype = i32
-        # watched columns: yuma_run_sched's arguments, the list, its length and B_watch after `out`
-        if hasattr(lib, "yuma_run_watch"):  # (A/B libraries of older sources lack them)
-            a = lib.yuma_run_sched.argtypes
-            lib.yuma_run_watch.argtypes = a[:13] + [vp, i32, vp] + a[13:]
-            lib.yuma_run_watch.restype = i32
-            a = lib.yuma_graph_create_sched.argtypes
-            lib.yuma_graph_create_watch.argtypes = a[:14] + [vp, i32, vp] + a[14:]
-            lib.yuma_graph_create_watch.restype = i32
-            lib.yuma_watch_native.argtypes = [i32, i32, i32, i32, i32, i32, i32]
-            lib.yuma_watch_native.restype = i32
-        # bond movement: yuma_run_watch's arguments with B_move after B_watch
-        if hasattr(lib, "yuma_run_move"):  # (A/B libraries of older sources lack them)
-            a = lib.yuma_run_watch.argtypes
-            lib.yuma_run_move.argtypes = a[:16] + [vp] + a[16:]
-            lib.yuma_run_move.restype = i32
-            a = lib.yuma_graph_create_watch.argtypes
-            lib.yuma_graph_create_move.argtypes = a[:17] + [vp] + a[17:]
-            lib.yuma_graph_create_move.restype = i32
-            lib.yuma_move_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
-            lib.yuma_move_native.restype = i32
-        # watched rows: yuma_run_move's arguments with the row list, its length and B_rows after B_move
-        if hasattr(lib, "yuma_run_rows"):  # (A/B libraries of older sources lack them)
-            a = lib.yuma_run_move.argtypes
-            lib.yuma_run_rows.argtypes = a[:17] + [vp, i32, vp] + a[17:]
-            lib.yuma_run_rows.restype = i32
-            a = lib.yuma_graph_create_move.argtypes
-            lib.yuma_graph_create_rows.argtypes = a[:18] + [vp, i32, vp] + a[18:]
-            lib.yuma_graph_create_rows.restype = i32
-            lib.yuma_rows_native.argtypes = [i32, i32, i32, i32, i32, i32, i32]
-            lib.yuma_rows_native.restype = i32
-        # row summary: yuma_run_rows's arguments with B_rowstat after B_rows
-        if hasattr(lib, "yuma_run_rowstat"):  # (A/B libraries of older sources lack them)
-            a = lib.yuma_run_rows.argtypes
-            lib.yuma_run_rowstat.argtypes = a[:20] + [vp] + a[20:]
-            lib.yuma_run_rowstat.restype = i32
-            a = lib.yuma_graph_create_rows.argtypes
-            lib.yuma_graph_create_rowstat.argtypes = a[:21] + [vp] + a[21:]
-            lib.yuma_graph_create_rowstat.restype = i32
-            lib.yuma_workspace_bytes_rowstat.argtypes = [i32, i32, i32, i32, i32, i32]
-            lib.yuma_workspace_bytes_rowstat.restype = sz
-            lib.yuma_rowstat_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
-            lib.yuma_rowstat_native.restype = i32
-        # reset events: yuma_run_opts's arguments, the list and its length after `out`
-        if hasattr(lib, "yuma_run_resets"):  # (A/B libraries of older sources lack them)
-            a = lib.yuma_run_opts.argtypes
-            lib.yuma_run_resets.argtypes = a[:11] + [vp, i32] + a[11:]
-            lib.yuma_run_resets.restype = i32
-            a = lib.yuma_graph_create_opts.argtypes
-            lib.yuma_graph_create_resets.argtypes = a[:12] + [vp, i32] + a[12:]
-            lib.yuma_graph_create_resets.restype = i32
-            lib.yuma_workspace_bytes_resets.argtypes = [i32, i32, i32, i32, i32, i32]
-            lib.yuma_workspace_bytes_resets.restype = sz
-            lib.yuma_resets_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
-            lib.yuma_resets_native.restype = i32
-        # validator-row events: yuma_run_resets's arguments, the second list and its length after n_events
-        if hasattr(lib, "yuma_run_events"):  # (A/B libraries of older sources lack them)
-            a = lib.yuma_run_resets.argtypes
-            lib.yuma_run_events.argtypes = a[:13] + [vp, i32] + a[13:]
-            lib.yuma_run_events.restype = i32
-            a = lib.yuma_graph_create_resets.argtypes
-            lib.yuma_graph_create_events.argtypes = a[:14] + [vp, i32] + a[14:]
-            lib.yuma_graph_create_events.restype = i32
-            lib.yuma_workspace_bytes_events.argtypes = [i32, i32, i32, i32, i32, i32]
-            lib.yuma_workspace_bytes_events.restype = sz
-            lib.yuma_events_native.argtypes = [i32, i32, i32, i32, i32, vp, i32]
-            lib.yuma_events_native.restype = i32
+        # The positional rungs: (name, base, position in the run's list, inserted types). Each rung's arguments are
+        # its base's with a few spliced in; its graph twin's are the same one place on (the handle comes first).
+        # With each, its yuma_<name>_native predicate and, where it has one, its yuma_workspace_bytes_<name>.
+        fp = ctypes.POINTER(ctypes.c_float)
+        if hasattr(lib, "yuma_run_sched"):  # input schedules: E and K in place of E, the schedule after S
+            lib.yuma_run_sched.argtypes = [i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, i32, vp, vp, fp]
+            lib.yuma_graph_create_sched.argtypes = [ctypes.POINTER(vp)] + lib.yuma_run_sched.argtypes[:-2]
+        rungs = (
+            ("watch", "sched", 13, [vp, i32, vp]),   # the list, its length and B_watch after `out`
+            ("move", "watch", 16, [vp]),             # B_move after B_watch
+            ("rows", "move", 17, [vp, i32, vp]),     # the row list, its length and B_rows after B_move
+            ("rowstat", "rows", 20, [vp]),           # B_rowstat after B_rows
+            ("resets", "opts", 11, [vp, i32]),       # the event list and its length after `out`
+            ("events", "resets", 13, [vp, i32]),     # the row event list and its length after n_events
+        )
+        for name, base, at, ins in rungs:
+            if not hasattr(lib, "yuma_run_" + name):  # (A/B libraries of older sources lack the later rungs)
+                continue
+            for prefix, k in (("yuma_run_", at), ("yuma_graph_create_", at + 1)):
+                a = getattr(lib, prefix + base).argtypes
+                getattr(lib, prefix + name).argtypes = a[:k] + ins + a[k:]
+        by_out, by_count = [i32, i32, i32, i32, i32, vp, i32], [i32] * 7  # (..., out, flags) / (..., n, flags)
+        native = {"sched": [i32] * 6 + [vp, i32], "watch": by_count, "move": by_out, "rows": by_count,
+                  "rowstat": by_out, "resets": by_out, "events": by_out}
+        for name, types in native.items():
+            if not hasattr(lib, "yuma_run_" + name):
+                continue
+            getattr(lib, "yuma_run_" + name).restype = i32
+            getattr(lib, "yuma_graph_create_" + name).restype = i32
+            getattr(lib, f"yuma_{name}_native").argtypes = types
+            getattr(lib, f"yuma_{name}_native").restype = i32
+            if name in ("sched", "rowstat", "resets", "events"):
+                fn = getattr(lib, "yuma_workspace_bytes_" + name)
+                fn.argtypes, fn.restype = [i32] * (7 if name == "sched" else 6), sz
+        if hasattr(lib, "yuma_run_request"):  # (A/B libraries of older sources lack them: _launch refuses those)
+            lib.yuma_run_request.argtypes = [vp, vp, fp]
+            lib.yuma_run_request.restype = i32
+            lib.yuma_graph_create_request.argtypes = [ctypes.POINTER(vp), vp]
+            lib.yuma_graph_create_request.restype = i32
+            lib.yuma_workspace_bytes_request.argtypes = [vp]
+            lib.yuma_workspace_bytes_request.restype = sz
         if hasattr(lib, "yuma_scan_plan"):  # (A/B libraries of older sources lack it)
             lib.yuma_scan_plan.argtypes = [i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp]
             lib.yuma_scan_plan.restype = i32
@@ -1243,65 +1228,37 @@ _OUT_SHAPES = {
 }
 
 
-def _launch(lib, dev, head, K, sched_dev, tail, opts, *, capture, phase_ms, watch=None, move=None,
-            resets=None, rows=None, row_events=None, rowstat=None) -> None:
-    """The run's one launch: yuma_run_opts, yuma_run_sched under a native
-    schedule, or yuma_run_watch with a native watch list (watch: the int32
-    device list, B_watch and the buffer whose address the engine gets); with `capture`, their yuma_graph_create_* twins,
-    the handle appended to it. head: variant, params, N, E; tail: V, M ...
-    chunk_epochs. move: B_move, for yuma_run_move (its watch list may be
-    absent: NULL, 0, NULL). resets: the int32 device event list [n, 4], for
-    yuma_run_resets (no schedule, watch list or B_move beside it). rows: the
-    int32 device row list, B_rows and the buffer whose address the engine gets,
-    for yuma_run_rows (its watch list and B_move may both be absent).
-    row_events: the int32 device row-event list [n, 4], for yuma_run_events
-    (yuma_run_resets's arguments, the second list after the first, which may be
-    absent: NULL, 0). rowstat: B_rowstat, for yuma_run_rowstat (yuma_run_rows's
-    arguments, B_rowstat after B_rows; no schedule and no B_move beside it, and
-    its watch and row lists may both be absent)."""
-    if rowstat is not None:
-        run_fn, graph_fn = lib.yuma_run_rowstat, lib.yuma_graph_create_rowstat
-        w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
-        rl = (None, 0, None) if rows is None else (rows[0].data_ptr(), rows[0].numel(), rows[2].data_ptr())
-        args = (head + (0,) + tail[:4] + (None,) + tail[4:7] + w + (None,) + rl + (rowstat.data_ptr(),) + tail[7:])
-    elif rows is not None:  # yuma_run_move's arguments (B_move may be NULL), the row list after B_move
-        run_fn, graph_fn = lib.yuma_run_rows, lib.yuma_graph_create_rows
-        w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
-        args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
-                + w + (_ptr(move),) + (rows[0].data_ptr(), rows[0].numel(), rows[2].data_ptr()) + tail[7:])
-    elif row_events is not None:  # yuma_run_resets's arguments, the row list and its length after n_events
-        run_fn, graph_fn = lib.yuma_run_events, lib.yuma_graph_create_events
-        n_ev, n_row = (0 if resets is None else resets.shape[0]), row_events.shape[0]
-        args = (head + tail[:7] + (resets.data_ptr() if n_ev else None, n_ev)
-                + (row_events.data_ptr() if n_row else None, n_row) + tail[7:])
-    elif resets is not None:  # yuma_run_opts's arguments, the list and its length after `out`
-        run_fn, graph_fn = lib.yuma_run_resets, lib.yuma_graph_create_resets
-        n_ev = resets.shape[0]
-        args = head + tail[:7] + (resets.data_ptr() if n_ev else None, n_ev) + tail[7:]
-    elif move is not None:  # yuma_run_watch's arguments, B_move after B_watch
-        run_fn, graph_fn = lib.yuma_run_move, lib.yuma_graph_create_move
-        w = (None, 0, None) if watch is None else (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr())
-        args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
-                + w + (move.data_ptr(),) + tail[7:])
-    elif watch is not None:  # yuma_run_sched's arguments (no schedule: NULL, K = 0), the list after `out`
-        run_fn, graph_fn = lib.yuma_run_watch, lib.yuma_graph_create_watch
-        args = (head + (0 if sched_dev is None else K,) + tail[:4] + (_ptr(sched_dev),) + tail[4:7]
-                + (watch[0].data_ptr(), watch[0].numel(), watch[2].data_ptr()) + tail[7:])
-    elif sched_dev is None:
-        run_fn, graph_fn, args = lib.yuma_run_opts, lib.yuma_graph_create_opts, head + tail
-    else:  # E and K in place of E, the schedule after S
-        run_fn, graph_fn = lib.yuma_run_sched, lib.yuma_graph_create_sched
-        args = head + (K,) + tail[:4] + (sched_dev.data_ptr(),) + tail[4:]
-    args += (ctypes.addressof(opts),)
+def _list_section(req: YumaRequestC, bit: int, names: tuple[str, str, str], arg) -> None:
+    """A watch or row list section of the request: arg is None, or the int32
+    device list, its history and the buffer whose address the engine gets."""
+    if arg is not None:
+        req.sections |= bit
+        for name, value in zip(names, (arg[0].data_ptr(), arg[0].numel(), arg[2].data_ptr())):
+            setattr(req, name, value)
+
+
+def _events_section(req: YumaRequestC, bit: int, names: tuple[str, str], events) -> None:
+    """An event section of the request: events is None or the int32 device
+    list [n, 4]; an empty list is no section (the run of yuma_run_opts)."""
+    if events is not None and events.shape[0] > 0:
+        req.sections |= bit
+        setattr(req, names[0], events.data_ptr())
+        setattr(req, names[1], events.shape[0])
+
+
+def _launch(lib, dev, req: YumaRequestC, *, capture, phase_ms) -> None:
+    """The run's one launch: yuma_run_request, or with `capture`
+    yuma_graph_create_request, the handle appended to it."""
     if capture is not None:  # RunGraph: capture instead of launching
         h = ctypes.c_void_p()
         torch.cuda.synchronize(dev)
-        _check(graph_fn(ctypes.byref(h), *args), graph_fn.__name__)
+        _check(lib.yuma_graph_create_request(ctypes.byref(h), ctypes.addressof(req)), "yuma_graph_create_request")
         capture.append(h)
         return
     # phase_ms (bench-only): per-phase device time from HIP events (blocks)
     buf = None if phase_ms is None else (ctypes.c_float * len(PHASES))()
-    _check(run_fn(*args, torch.cuda.current_stream(dev).cuda_stream, buf), run_fn.__name__)
+    _check(lib.yuma_run_request(ctypes.addressof(req), torch.cuda.current_stream(dev).cuda_stream, buf),
+           "yuma_run_request")
     if phase_ms is not None:
         phase_ms[:] = list(buf)
 
@@ -1695,20 +1652,28 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
         b_rows = torch.empty((len(h_epochs), N, rows_host.numel(), M), dtype=torch.float32, device=dev)
         # (no stored epoch: nothing is written, but the engine refuses a null B_rows)
         rows_arg = (rows_dev, b_rows, b_rows if h_epochs else torch.empty(4, dtype=torch.float32, device=dev))
-    full = o.get("Tv") is not None
+    outs = YumaOutputsC(**{k: _ptr(o.get(k)) for k in OUTPUT_FIELDS})
+    # the run as one record: the sizes and sections size the workspace, then the record is the launch
+    req = YumaRequestC(struct_size=ctypes.sizeof(YumaRequestC), variant=variant, N=N, E=E, V=V, M=M,
+                       params_dev=prm.data_ptr(), W=W.data_ptr(), S=S.data_ptr(), B_init=_ptr(B_init),
+                       Wprev_init=_ptr(Wprev_init), out=ctypes.addressof(outs), chunk_epochs=int(chunk_epochs))
+    if sched_dev is not None:
+        req.K, req.sched_dev = K, sched_dev.data_ptr()
+    _list_section(req, REQ_WATCH, ("watch_dev", "n_watch", "B_watch"), watch_arg)
+    _list_section(req, REQ_ROWS, ("rows_dev", "n_rows", "B_rows"), rows_arg)
+    if b_move is not None:
+        req.sections, req.B_move = req.sections | REQ_MOVE, b_move.data_ptr()
     if b_rowstat is not None:
-        nbytes = workspace_bytes_rowstat(variant, N, E, V, M, full)
-    elif sched_dev is not None:
-        nbytes = workspace_bytes_sched(variant, N, E, K, V, M, full)
-    elif rowev_dev is not None and rowev_dev.shape[0] > 0:
-        nbytes = int(lib.yuma_workspace_bytes_events(variant, N, E, V, M, 1 if full else 0))
-    elif resets_dev is not None and resets_dev.shape[0] > 0:
-        nbytes = int(lib.yuma_workspace_bytes_resets(variant, N, E, V, M, 1 if full else 0))
-    else:
-        nbytes = workspace_bytes(variant, N, E, V, M, full)
+        req.sections, req.B_rowstat = req.sections | REQ_ROWSTAT, b_rowstat.data_ptr()
+    _events_section(req, REQ_RESETS, ("events_dev", "n_events"), resets_dev)
+    _events_section(req, REQ_ROW_EVENTS, ("row_events_dev", "n_row_events"), rowev_dev)
+    if not hasattr(lib, "yuma_run_request"):
+        raise EngineUnavailable("this library has no yuma_run_request: it was built from older sources; run it with "
+                                "the engine.py of those sources")
+    nbytes = int(lib.yuma_workspace_bytes_request(ctypes.addressof(req)))
     if workspace is None or workspace.numel() < nbytes:
         workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    outs = YumaOutputsC(**{k: _ptr(o.get(k)) for k in OUTPUT_FIELDS})
+    req.workspace, req.workspace_bytes = workspace.data_ptr(), workspace.numel()
     if single_call:  # one Yuma* call per slice: the yuma_epoch entry point
         if E != 1 or capture is not None or phase_ms is not None:
             raise ValueError("single_call is one epoch, launched directly")
@@ -1720,11 +1685,8 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
                                | (RUN_HIST_BF16 if hist_native else 0),
                                # (a stride of E or more stores one epoch at the most: int32 either way)
                                hist_stride=min(int(hist_stride), E), hist_first=h_epochs[0] if h_epochs else E)
-        _launch(lib, dev, (variant, prm.data_ptr(), N, E), K, sched_dev,
-                (V, M, W.data_ptr(), S.data_ptr(), _ptr(B_init), _ptr(Wprev_init), ctypes.addressof(outs),
-                 workspace.data_ptr(), workspace.numel(), int(chunk_epochs)), opts,
-                capture=capture, phase_ms=phase_ms, watch=watch_arg, move=b_move, resets=resets_dev, rows=rows_arg,
-                row_events=rowev_dev, rowstat=b_rowstat)
+        req.opts = ctypes.addressof(opts)
+        _launch(lib, dev, req, capture=capture, phase_ms=phase_ms)
     keep = {k: v for k, v in o.items() if k not in ("Dn", "C", "I", "B_final", "B_hist")}
     # keep inputs alive until the stream has consumed them
     keep["_inputs"] = (W, S, B_init, Wprev_init, prm, workspace)
@@ -1772,7 +1734,7 @@ def run(variant: int, params: list[YumaParamsC], W: torch.Tensor, S: torch.Tenso
 
 
 class RunGraph:
-    """A whole `run` captured once into a HIP graph (yuma_graph_create_opts) and
+    """A whole `run` captured once into a HIP graph (yuma_graph_create_request) and
     replayed with one launch per call: the E-epoch loop of run_simulation
     (simulation_utils.py:52-110) with no host work between phases or epochs.
     Inputs and outputs are the buffers of the capture (`result`); refill the
