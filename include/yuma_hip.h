@@ -997,6 +997,80 @@ int yuma_shard_stage(int stage, int variant, const yuma_params_t* params_dev, in
 int yuma_synth_weights(uint64_t seed, int E, int N, int V, int M, int t0, float* W,
                        void* stream);
 
+/* ------------------------------------------------------------------------
+ * Weight pairs: the dense uint16 W built on the device.
+ *
+ * The chain stores a validator's weights as a short list of (uid: u16,
+ * weight: u16) pairs, not as a dense row. yuma_weights_from_pairs builds the
+ * dense uint16 matrix YUMA_RUN_W_U16 reads from such lists in CSR form: `rows`
+ * is E * N * V flattened, so W [rows][M] is the [E][N][V][M] tensor a run
+ * takes. Every pointer addresses device memory. The call is stream-ordered,
+ * allocates nothing, never synchronises and can be captured into a graph: it
+ * is a chain of kernel launches (status zero, fill, scatter, read-back).
+ *
+ * Row ranges. Row r owns the pairs [row_ptr[r], row_ptr[r + 1]). The host
+ * cannot check a list in device memory: the device code clamps the start into
+ * [0, nnz] and the end into [start, nnz] before it addresses anything. A row
+ * whose range had to be clamped is a bad row: its clamped range is still
+ * applied, and it counts once in status[YUMA_PAIRS_ST_BAD_ROWS]. No input
+ * makes the engine touch memory outside uid[0 .. nnz), val[0 .. nnz),
+ * row_ptr[0 .. rows] or W[0 .. rows * M).
+ *
+ * Stored values. Every element of W is written; a column no pair names is 0.
+ * A pair with uid >= M (a deregistered UID) is dropped and counted in
+ * status[YUMA_PAIRS_ST_DROPPED].
+ *
+ * Duplicates. Two pairs of one row with the same uid and the same weight are
+ * harmless. With different weights the element holds one of them, unspecified
+ * which, and the row counts once in status[YUMA_PAIRS_ST_CONFLICT_ROWS]. The
+ * count is taken by reading the row back after the scatter: a row has a
+ * conflict exactly when some in-range pair differs from what its element
+ * holds, which is well defined whichever weight won. With status NULL the
+ * read-back is not launched.
+ *
+ * YUMA_PAIRS_UPSCALE: the chain's max-upscale, per row. rowmax is the maximum
+ * weight over the row's in-range pairs; the stored value is
+ * round_half_even(weight * 65535 / rowmax) in exact integer arithmetic
+ * (n = weight * 65535, q = n / rowmax, r = n % rowmax, q + 1 when 2 r > rowmax
+ * or when 2 r == rowmax and q is odd): the bits of
+ * yuma_simulation's engine.to_u16 (float64 rint) on the densified row. A row
+ * whose rowmax is 0 stays 0. A conflict is judged on the raw weights (the
+ * scale is at least 1, so different weights of a row store different values).
+ *
+ * Status: NULL, or YUMA_PAIRS_ST_WORDS 32-bit words. The engine zeroes them
+ * itself with a kernel on the stream (not a memset node: a captured call
+ * stays a chain of kernel nodes and every replay starts from zero), then adds
+ * with vector atomics, modulo 2^32. Word 3 stays 0.
+ *
+ * Alignment: W, uid and val 2 bytes, status 4, row_ptr 8. The fill stores 16
+ * bytes per lane where M % 8 == 0 and W is 16-byte aligned, else 2 bytes; the
+ * choice is made on the host from the pointer and M.
+ *
+ * Refusals, all YUMA_EINVAL, before the first launch and without a HIP call,
+ * in this order: rows < 0; M < 1; nnz < 0; a NULL row_ptr, then W, with
+ * rows > 0; a NULL uid, then val, with nnz > 0; an unknown flag; rows * M
+ * above 2^62 elements (the kernels index W in signed 64 bits; the bound keeps
+ * a byte offset and an index one grid stride past the end inside them); a
+ * pointer off the alignment above. rows == 0 is then a successful no-op: no
+ * launch, status untouched. (No reference counterpart: the reference takes
+ * dense float weights only.)
+ * ---------------------------------------------------------------------- */
+enum yuma_pairs_flags { YUMA_PAIRS_UPSCALE = 1 };
+enum {
+  YUMA_PAIRS_ST_DROPPED = 0,
+  YUMA_PAIRS_ST_CONFLICT_ROWS = 1,
+  YUMA_PAIRS_ST_BAD_ROWS = 2,
+  YUMA_PAIRS_ST_WORDS = 4
+};
+int yuma_weights_from_pairs(long long rows, int M, long long nnz,
+                            const int64_t* row_ptr,   /* [rows + 1], device */
+                            const uint16_t* uid,      /* [nnz], device */
+                            const uint16_t* val,      /* [nnz], device */
+                            int flags,
+                            uint16_t* W,              /* [rows][M], device */
+                            uint32_t* status,         /* [YUMA_PAIRS_ST_WORDS], device, or NULL */
+                            void* stream);
+
 const char* yuma_last_error(void);
 const char* yuma_version(void);
 /* Build identity of this library: "src-" + the first 16 hex digits of the

@@ -6079,6 +6079,138 @@ __global__ void k_synth(uint64_t seed, int E, int N, int V, int M, int t0, float
   }
 }
 
+// ---------------------------------------------------------------------------
+// Weight pairs (yuma_weights_from_pairs): the dense uint16 W of the chain's
+// per-row (uid, weight) lists. Four stream-ordered launches: the status words
+// to zero (k_pairs_zero: a kernel, not a memset node, as k_move_zero), every
+// element of W to zero (k_pairs_fill), the pairs into their rows
+// (k_pairs_scatter), each pair against what its row now holds
+// (k_pairs_check). The scatter follows the fill and the read-back the scatter
+// by launch order alone: nothing rests on the order in which the memory system
+// retires two lanes' stores to one address, and no fence or vmcnt wait is
+// hand-placed. The scatter and the check give a wave to a row and stride over
+// the rows; a wave's lanes stride over the row's pairs 64 at a time.
+// ---------------------------------------------------------------------------
+constexpr int kPairsWaves = 1024;  // waves of the scatter and check grids: 256 blocks of 4
+
+// (a template, so that the compiler emits it behind every kernel of before:
+// as the last plain kernel of the file it would move quantile_of<256>, which
+// follows that one, inside its 256-byte slot and change the call offsets in
+// k_quantise and k_liquid)
+template <int WORDS>
+__global__ void k_pairs_zero(unsigned* status) {
+  if (threadIdx.x < WORDS) status[threadIdx.x] = 0u;
+}
+
+// n elements from W to zero: VEC (n % 8 == 0, W 16-byte aligned: the host's
+// choice) 16 bytes per lane, else 2 bytes per lane. Plain stores.
+template <bool VEC>
+__global__ __launch_bounds__(1024) void k_pairs_fill(unsigned short* __restrict__ W, long long n) {
+  const long long stride = (long long)gridDim.x * 1024;
+  const long long i0 = (long long)blockIdx.x * 1024 + threadIdx.x;
+  if constexpr (VEC) {
+    uint4* p = reinterpret_cast<uint4*>(W);
+    for (long long i = i0; i < n / 8; i += stride) p[i] = uint4{0u, 0u, 0u, 0u};
+  } else {
+    for (long long i = i0; i < n; i += stride) W[i] = 0;
+  }
+}
+
+// Row r's pairs [b, e): row_ptr's two entries clamped before they address
+// anything, the start into [0, nnz] and the end into [start, nnz]. True when
+// either had to move (a bad row).
+__device__ __forceinline__ bool pairs_range(const long long* __restrict__ row_ptr, long long r, long long nnz,
+                                            long long& b, long long& e) {
+  const long long b0 = row_ptr[r], e0 = row_ptr[r + 1];
+  b = min(max(b0, 0ll), nnz);
+  e = min(max(e0, b), nnz);
+  return b != b0 || e != e0;
+}
+
+// the maximum weight over the row's in-range pairs, in every lane
+__device__ __forceinline__ unsigned pairs_rowmax(const unsigned short* __restrict__ uid,
+                                                 const unsigned short* __restrict__ val, long long b, long long e,
+                                                 int M, int lane) {
+  unsigned mx = 0u;
+  for (long long p = b + lane; p < e; p += 64)
+    if ((int)uid[p] < M) mx = max(mx, (unsigned)val[p]);
+  for (int o = 1; o < 64; o <<= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
+  return mx;
+}
+
+// The stored value of weight v. UP: round_half_even(v * 65535 / rowmax) in
+// exact 32-bit integers (v <= rowmax <= 65535, so v * 65535 < 2^32 and 2 r
+// < 2^17); rowmax 0 (then v is 0) stays 0. The factor 65535 / rowmax is >= 1,
+// so two different weights of a row never round to one value: comparing
+// stored values is comparing raw ones (k_pairs_check).
+template <bool UP>
+__device__ __forceinline__ unsigned pairs_value(unsigned v, unsigned rowmax) {
+  if (!UP) return v;
+  if (rowmax == 0u) return 0u;
+  const unsigned n = v * 65535u, q = n / rowmax, r = n % rowmax;
+  return q + ((2u * r > rowmax || (2u * r == rowmax && (q & 1u))) ? 1u : 0u);
+}
+
+__device__ __forceinline__ long long pairs_wave() {
+  return (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+}
+
+// The scatter: W[r][uid] = value of every in-range pair; a uid >= M is dropped
+// and counted. status (or NULL): [DROPPED] += the dropped pairs, [BAD_ROWS] +=
+// the rows whose range was clamped, one vector atomic add per wave each.
+template <bool UP>
+__global__ __launch_bounds__(256) void k_pairs_scatter(long long rows, int M, long long nnz,
+                                                       const long long* __restrict__ row_ptr,
+                                                       const unsigned short* __restrict__ uid,
+                                                       const unsigned short* __restrict__ val,
+                                                       unsigned short* __restrict__ W, unsigned* status) {
+  const int lane = threadIdx.x & 63;
+  const long long waves = (long long)gridDim.x * 4;
+  unsigned dropped = 0u, bad = 0u;
+  for (long long r = pairs_wave(); r < rows; r += waves) {
+    long long b, e;
+    bad += pairs_range(row_ptr, r, nnz, b, e) ? 1u : 0u;
+    const unsigned rowmax = UP ? pairs_rowmax(uid, val, b, e, M, lane) : 0u;
+    unsigned short* row = W + r * M;
+    for (long long p = b + lane; p < e; p += 64) {
+      const int u = uid[p];
+      if (u < M) row[u] = (unsigned short)pairs_value<UP>(val[p], rowmax);
+      else ++dropped;
+    }
+  }
+  if (status == nullptr) return;
+  for (int o = 1; o < 64; o <<= 1) dropped += (unsigned)__shfl_xor((int)dropped, o, 64);
+  if (lane == 0 && dropped != 0u) atomicAdd(status + YUMA_PAIRS_ST_DROPPED, dropped);
+  if (lane == 0 && bad != 0u) atomicAdd(status + YUMA_PAIRS_ST_BAD_ROWS, bad);
+}
+
+// The read-back: a row has a conflict exactly when some in-range pair differs
+// from what its element holds (whichever duplicate won). status[CONFLICT_ROWS]
+// += those rows, one vector atomic add per wave.
+template <bool UP>
+__global__ __launch_bounds__(256) void k_pairs_check(long long rows, int M, long long nnz,
+                                                     const long long* __restrict__ row_ptr,
+                                                     const unsigned short* __restrict__ uid,
+                                                     const unsigned short* __restrict__ val,
+                                                     const unsigned short* __restrict__ W, unsigned* status) {
+  const int lane = threadIdx.x & 63;
+  const long long waves = (long long)gridDim.x * 4;
+  unsigned conflicts = 0u;
+  for (long long r = pairs_wave(); r < rows; r += waves) {
+    long long b, e;
+    pairs_range(row_ptr, r, nnz, b, e);
+    const unsigned rowmax = UP ? pairs_rowmax(uid, val, b, e, M, lane) : 0u;
+    const unsigned short* row = W + r * M;
+    bool differs = false;
+    for (long long p = b + lane; p < e; p += 64) {
+      const int u = uid[p];
+      if (u < M) differs |= (unsigned)row[u] != pairs_value<UP>(val[p], rowmax);
+    }
+    conflicts += __any(differs) ? 1u : 0u;
+  }
+  if (lane == 0 && conflicts != 0u) atomicAdd(status + YUMA_PAIRS_ST_CONFLICT_ROWS, conflicts);
+}
+
 }  // namespace yk
 
 // ===========================================================================
@@ -8191,6 +8323,45 @@ int yuma_synth_weights(uint64_t seed, int E, int N, int V, int M, int t0, float*
   long long blocks = (total + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   YK_LAUNCH(yk::k_synth, blocks, 256, stream, seed, E, N, V, M, t0, W);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(YUMA_EHIP, "HIP launch failed: %s", hipGetErrorString(e));
+  return YUMA_OK;
+}
+
+int yuma_weights_from_pairs(long long rows, int M, long long nnz, const int64_t* row_ptr, const uint16_t* uid,
+                            const uint16_t* val, int flags, uint16_t* W, uint32_t* status, void* stream) {
+  if (rows < 0) return fail(YUMA_EINVAL, "rows=%lld must not be negative", rows);
+  if (M < 1) return fail(YUMA_EINVAL, "M=%d must be at least 1", M);
+  if (nnz < 0) return fail(YUMA_EINVAL, "nnz=%lld must not be negative", nnz);
+  if (rows > 0 && row_ptr == nullptr) return fail(YUMA_EINVAL, "row_ptr is NULL with rows=%lld", rows);
+  if (rows > 0 && W == nullptr) return fail(YUMA_EINVAL, "W is NULL with rows=%lld", rows);
+  if (nnz > 0 && uid == nullptr) return fail(YUMA_EINVAL, "uid is NULL with nnz=%lld", nnz);
+  if (nnz > 0 && val == nullptr) return fail(YUMA_EINVAL, "val is NULL with nnz=%lld", nnz);
+  if ((flags & ~YUMA_PAIRS_UPSCALE) != 0) return fail(YUMA_EINVAL, "flags=%d holds an unknown flag", flags);
+  // the kernels index W's elements and count their strides in signed 64 bits:
+  // below 2^62 elements a byte offset, and an index one grid stride past the
+  // end, still fit
+  if (rows > (1ll << 62) / M) return fail(YUMA_EINVAL, "rows * M = %lld * %d exceeds 2^62 elements", rows, M);
+  if ((((uintptr_t)W | (uintptr_t)uid | (uintptr_t)val) & 1u) != 0 || ((uintptr_t)row_ptr & 7u) != 0 ||
+      ((uintptr_t)status & 3u) != 0)
+    return fail(YUMA_EINVAL, "W, uid and val must be 2-byte, status 4-byte and row_ptr 8-byte aligned");
+  if (rows == 0) return YUMA_OK;
+  const hipStream_t st = (hipStream_t)stream;
+  unsigned* stw = reinterpret_cast<unsigned*>(status);
+  const long long* rp = reinterpret_cast<const long long*>(row_ptr);
+  if (stw != nullptr) YK_LAUNCH(yk::k_pairs_zero<YUMA_PAIRS_ST_WORDS>, 1, 64, st, stw);
+  const long long n = rows * M;
+  const bool vec = (M & 7) == 0 && aligned16(W);
+  const long long fb = ((vec ? n / 8 : n) + 1023) / 1024;
+  with_bool(vec, [&](auto VEC) {
+    YK_LAUNCH((yk::k_pairs_fill<decltype(VEC)::value>), fb < 256 ? fb : 256, 1024, st, W, n);
+  });
+  const long long wb = (rows + 3) / 4 < yk::kPairsWaves / 4 ? (rows + 3) / 4 : yk::kPairsWaves / 4;
+  with_bool((flags & YUMA_PAIRS_UPSCALE) != 0, [&](auto UP) {
+    YK_LAUNCH((yk::k_pairs_scatter<decltype(UP)::value>), wb, 256, st, rows, M, nnz, rp, uid, val, W, stw);
+    if (stw != nullptr)
+      YK_LAUNCH((yk::k_pairs_check<decltype(UP)::value>), wb, 256, st, rows, M, nnz, rp, uid, val, W, stw);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(YUMA_EHIP, "HIP launch failed: %s", hipGetErrorString(e));
   return YUMA_OK;

@@ -39,6 +39,8 @@ RUN_W_U16 = 2  # ... W holds uint16 elements (the on-chain weight format), read 
 RUN_HIST_BF16 = 4  # ... B_hist holds bfloat16 elements, written by the bond scan
 LIQUID_OFF, LIQUID_QUANTILE, LIQUID_CONST_AB = range(3)
 OVR_HIGH, OVR_LOW, OVR_FORCE_Q99 = 1, 2, 4
+PAIRS_UPSCALE = 1  # yuma_weights_from_pairs flags
+PAIRS_ST_DROPPED, PAIRS_ST_CONFLICT_ROWS, PAIRS_ST_BAD_ROWS, PAIRS_ST_WORDS = 0, 1, 2, 4  # ... its status words
 
 EXPORTED_SYMBOLS = (
     "yuma_workspace_bytes",
@@ -78,6 +80,7 @@ EXPORTED_SYMBOLS = (
     "yuma_scan_plan",
     "yuma_epoch",
     "yuma_synth_weights",
+    "yuma_weights_from_pairs",
     "yuma_shard_stage",
     "yuma_graph_create",
     "yuma_graph_create_ex",
@@ -260,6 +263,10 @@ def load_library(path: str | None = None):
         lib.yuma_shard_stage.restype = i32
         lib.yuma_synth_weights.argtypes = [ctypes.c_uint64, i32, i32, i32, i32, i32, vp, vp]
         lib.yuma_synth_weights.restype = i32
+        if hasattr(lib, "yuma_weights_from_pairs"):  # (A/B libraries of older sources lack it: the call refuses those)
+            lib.yuma_weights_from_pairs.argtypes = [ctypes.c_longlong, i32, ctypes.c_longlong, vp, vp, vp, i32, vp,
+                                                    vp, vp]
+            lib.yuma_weights_from_pairs.restype = i32
         lib.yuma_graph_create.argtypes = [ctypes.POINTER(vp), i32, vp, i32, i32, i32, i32, vp, vp,
                                           vp, vp, vp, vp, sz, i32]
         lib.yuma_graph_create.restype = i32
@@ -1109,6 +1116,103 @@ def to_u16(W: torch.Tensor) -> torch.Tensor:
     # tie reaches the rounding as a tie; an all-zero row divides by 1
     q = w * 65535.0 / torch.where(mx > 0, mx, torch.ones_like(mx))
     return torch.from_numpy(np.rint(q.numpy()).astype(np.uint16))  # rint: half to even
+
+
+def _as_u16(x: torch.Tensor) -> torch.Tensor:
+    """Integers in [0, 65535] of any integer dtype as torch.uint16 (torch has
+    no arithmetic on uint16: the value's low 16 bits through int16)."""
+    x = x.to(torch.int64)
+    return ((x + 32768) % 65536 - 32768).to(torch.int16).view(torch.uint16)
+
+
+def pairs_from_dense(W: torch.Tensor):
+    """(row_ptr int64 [rows + 1], uid uint16 [nnz], val uint16 [nnz]): the
+    nonzeros of a uint16 tensor whose last dimension is M, rows (every leading
+    dimension flattened) in order and each row's columns ascending -- the CSR
+    pair lists yuma_weights_from_pairs takes, on W's device. The inverse of
+    weights_from_pairs on lists without zero weights, dropped uids or
+    duplicates. M > 65536 raises ValueError: a uid would not fit 16 bits."""
+    if not isinstance(W, torch.Tensor) or W.dtype != torch.uint16 or W.dim() < 1:
+        raise ValueError("pairs_from_dense takes a torch.uint16 tensor of at least one dimension")
+    M = W.shape[-1]
+    if M < 1 or M > 65536:
+        raise ValueError(f"M={M} must lie in [1, 65536]: a uid beyond that would not fit 16 bits")
+    w = W.contiguous().view(torch.int16).reshape(-1, M)
+    nz = w != 0
+    row_ptr = torch.zeros(w.shape[0] + 1, dtype=torch.int64, device=W.device)
+    torch.cumsum(nz.sum(dim=1), dim=0, out=row_ptr[1:])
+    idx = nz.nonzero()  # row-major: rows in order, columns ascending
+    return row_ptr, _as_u16(idx[:, 1]), w[nz].view(torch.uint16)
+
+
+@dataclass(frozen=True)
+class PairsStatus:
+    """The status words of one weights_from_pairs call (include/yuma_hip.h)."""
+    dropped: int        # pairs with uid >= M
+    conflict_rows: int  # rows holding one uid with two different weights
+    bad_rows: int       # rows whose row_ptr range had to be clamped
+
+    @classmethod
+    def from_tensor(cls, status: torch.Tensor) -> "PairsStatus":
+        """Reads the device words: the one place that synchronises."""
+        h = [int(x) & 0xFFFFFFFF for x in status.detach().cpu().tolist()]
+        return cls(dropped=h[PAIRS_ST_DROPPED], conflict_rows=h[PAIRS_ST_CONFLICT_ROWS],
+                   bad_rows=h[PAIRS_ST_BAD_ROWS])
+
+
+def weights_from_pairs(row_ptr: torch.Tensor, uid: torch.Tensor, val: torch.Tensor, shape, *,
+                       upscale: bool = False, out: torch.Tensor | None = None, want_status: bool = True,
+                       stream: "torch.cuda.Stream | None" = None):
+    """The dense torch.uint16 W of the chain's (uid, weight) pair lists, built
+    on the device (yuma_weights_from_pairs): (W, status).
+
+    row_ptr int64 [rows + 1], uid and val uint16 [nnz], CPU or device: row r
+    (of `shape`'s leading dimensions flattened; (E, N, V, M) for a run) owns the
+    pairs [row_ptr[r], row_ptr[r + 1]). shape's last dimension is M. upscale:
+    the chain's per-row max-upscale, the bits of to_u16 on the densified row.
+    out: a contiguous device torch.uint16 tensor of that shape to fill (any
+    2-byte alignment). status: a device int32[4] tensor for
+    PairsStatus.from_tensor (dropped pairs, rows with conflicting duplicates,
+    rows with a clamped range), or None with want_status=False, which also
+    skips the read-back pass. stream: a torch.cuda.Stream, default the current
+    one. Nothing here synchronises; what cannot be checked without reading the
+    lists (row_ptr's values) is clamped on the device and reported in status.
+    Dtypes, dimensions and lengths raise ValueError before the library is
+    touched."""
+    for name, t, dt in (("row_ptr", row_ptr, torch.int64), ("uid", uid, torch.uint16), ("val", val, torch.uint16)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1:
+            raise ValueError(f"{name} must be a one-dimensional {dt} tensor, not "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__}")
+    try:
+        shape = tuple(operator.index(s) for s in shape)
+    except TypeError as e:
+        raise ValueError(f"shape must be a sequence of integers: {e}") from e
+    if not shape or min(shape) < 0 or shape[-1] < 1:
+        raise ValueError(f"shape {shape} must be non-negative sizes ending in M >= 1")
+    M, rows = shape[-1], math.prod(shape[:-1])
+    if row_ptr.numel() != rows + 1:
+        raise ValueError(f"row_ptr holds {row_ptr.numel()} entries; shape {shape} has {rows} rows and needs {rows + 1}")
+    if uid.numel() != val.numel():
+        raise ValueError(f"uid holds {uid.numel()} entries and val {val.numel()}")
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint16
+                            or tuple(out.shape) != shape or not out.is_contiguous() or not out.is_cuda):
+        raise ValueError(f"out must be a contiguous device torch.uint16 tensor of shape {shape}")
+    if stream is not None and not isinstance(stream, torch.cuda.Stream):
+        raise ValueError(f"stream must be a torch.cuda.Stream, not {type(stream).__name__}")
+    dev = device()
+    lib = load_library()
+    if not hasattr(lib, "yuma_weights_from_pairs"):
+        raise EngineError("this libyuma_hip.so lacks yuma_weights_from_pairs")
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        rp, u, v = (t.detach().to(dev).contiguous() for t in (row_ptr, uid, val))
+        W = out if out is not None else torch.empty(shape, dtype=torch.uint16, device=dev)
+        # (rows == 0 launches nothing: the words are zero from the start)
+        status = (torch.zeros if rows == 0 else torch.empty)(PAIRS_ST_WORDS, dtype=torch.int32, device=dev) \
+            if want_status else None
+        _check(lib.yuma_weights_from_pairs(rows, M, u.numel(), rp.data_ptr(), u.data_ptr(), v.data_ptr(),
+                                           PAIRS_UPSCALE if upscale else 0, W.data_ptr(), _ptr(status),
+                                           torch.cuda.current_stream(dev).cuda_stream), "yuma_weights_from_pairs")
+    return W, status
 
 
 def hist_epochs(E: int, stride: int = 1, first: int | None = None) -> tuple[int, ...]:
