@@ -333,7 +333,7 @@ def test_run_simulations_rejects_the_combinations_before_touching_the_device(no_
 # the register report of the RL kernels, from the built library's code object
 # ---------------------------------------------------------------------------
 def test_no_rl_kernel_spills_or_uses_scratch():
-    """The 12 k_bonds_elem<.., RL> forms report no spilled VGPR, no spilled SGPR
+    """The 12 RL forms of k_bonds_elem report no spilled VGPR, no spilled SGPR
     and no scratch. Two empty asm statements steer their register classes
     (the AND mask and the table pointer's step in vector registers): a compiler
     that stops honouring them shows here, not only in profiles/resets/."""
@@ -343,10 +343,10 @@ def test_no_rl_kernel_spills_or_uses_scratch():
     import kcompare
 
     meta = kcompare.kernels(engine.LIB_PATH)
-    rl = {k: v[2] for k, v in meta.items() if "k_bonds_elem" in k and "BondArgsRl" in k
-          and re.search(r"Lb1EEEvNSt11conditional", k)}
+    forms = kcompare.elem_forms(meta, "RL")
+    rl = {k: meta[k][2] for k in forms}
     assert len(rl) == 12, sorted(rl)
-    assert sorted({re.search(r"k_bonds_elemILi(\d)", k).group(1) for k in rl}) == ["3", "4"]
+    assert sorted({variant for variant, _, _ in forms.values()}) == ["3", "4"]
     fields = dict(zip(kcompare.FIELDS, range(len(kcompare.FIELDS))))
     for name, m in rl.items():
         for f in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):

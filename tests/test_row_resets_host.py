@@ -351,25 +351,23 @@ def test_run_simulations_rejects_the_combinations_before_touching_the_device(no_
 # the register report of the row-event kernels, from the built library's code object
 # ---------------------------------------------------------------------------
 def test_no_row_event_kernel_spills_or_uses_scratch():
-    """The 12 k_bonds_elem<.., RW = true, RL = false> forms -- the twins of the
-    12 RL forms, read the way tests/test_resets_host.py reads those -- report no
-    spilled VGPR, no spilled SGPR and no scratch, and take BondArgsRl's block
-    with the second pointer appended."""
+    """The 12 RW forms of k_bonds_elem -- the twins of the 12 RL forms, read the
+    way tests/test_resets_host.py reads those -- report no spilled VGPR, no
+    spilled SGPR and no scratch, and take the RL forms' block with the second
+    pointer appended."""
     import sys
 
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kcompare
 
     meta = kcompare.kernels(engine.LIB_PATH)
-    tail = lambda k: re.search(r"k_bonds_elemILi(\d)ENS_9ElemShapeI(.*?)EEE(.*?)Lb([01])ELb([01])EEEvNSt11conditional", k)
-    rw = {k: v[2] for k, v in meta.items() if "k_bonds_elem" in k and "BondArgsRw" in k and tail(k)
-          and tail(k).group(4, 5) == ("1", "0")}
-    rl = {k for k in meta if "k_bonds_elem" in k and "BondArgsRw" in k and tail(k) and tail(k).group(4, 5) == ("0", "1")}
+    forms, rl = kcompare.elem_forms(meta, "RW"), set(kcompare.elem_forms(meta, "RL"))
+    rw = {k: meta[k][2] for k in forms}
     assert len(rw) == 12 and len(rl) == 12, sorted(rw)
-    assert {tail(k).group(1, 2, 3) for k in rw} == {tail(k).group(1, 2, 3) for k in rl}   # the twins, shape by shape
-    assert sorted({tail(k).group(1) for k in rw}) == ["3", "4"]
+    assert {kcompare.with_form(k, "RW", "RL") for k in rw} == rl   # the twins, shape by shape
+    assert sorted({variant for variant, _, _ in forms.values()}) == ["3", "4"]
     fields = dict(zip(kcompare.FIELDS, range(len(kcompare.FIELDS))))
     for name, m in rw.items():
         for f in ("vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size"):
             assert m[fields[f]] == "0", (name, f, m)
-        assert m[fields["kernarg_segment_size"]] == "232", (name, m)   # BondArgsRl's 224 bytes and the row table pointer
+        assert m[fields["kernarg_segment_size"]] == "232", (name, m)   # the RL forms' 224 bytes and the row table pointer

@@ -235,18 +235,18 @@ def test_scan_plan_record_is_untouched():
 # ---------------------------------------------------------------------------
 def test_no_rs_kernel_spills_or_uses_scratch():
     """The 4 row-summary forms of k_bonds_elem (Yuma 3 / Yuma 4 on the one-row and
-    the two-row flat shape, an ElemShapeRs each) report no spilled VGPR, no
-    spilled SGPR and no scratch, and take BondArgs' block with the two pointers
-    appended."""
+    the two-row flat shape) report no spilled VGPR, no spilled SGPR and no
+    scratch, and take BondArgs' block with the two pointers appended."""
     import sys
 
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kcompare
 
     meta = kcompare.kernels(engine.LIB_PATH)
-    rs = {k: v[2] for k, v in meta.items() if "k_bonds_elem" in k and "ElemShapeRsI" in k}
+    forms = kcompare.elem_forms(meta, "RS")
+    rs = {k: meta[k][2] for k in forms}
     assert len(rs) == 4, sorted(rs)
-    shapes = {re.search(r"k_bonds_elemILi(\d)ENS_11ElemShapeRsILi(\d)E", k).group(1, 2) for k in rs}
+    shapes = {(variant, re.match(r"Li(\d)E", shape).group(1)) for variant, shape, _ in forms.values()}
     assert shapes == {("3", "1"), ("3", "2"), ("4", "1"), ("4", "2")}
     fields = dict(zip(kcompare.FIELDS, range(len(kcompare.FIELDS))))
     for name, m in rs.items():

@@ -25,8 +25,8 @@ PATCHES["grp_k1_r4_w4"] = [("constexpr int kScanGroup = 4;", "constexpr int kSca
 # epoch loop, so the waitcnt pass need not drain the ring in the loop
 _ELEM_PRE = """#pragma unroll
   for (int k = 0; k < P; ++k)
-    if (A.t0 + k < A.t1) fetch(k, A.t0 + k, sched_at(A.t0 + k));
-  int snext = sched_at(A.t0 + P);  // SC: the slice of the next epoch to fetch
+    if (A.t0 + k < A.t1) fetch(k, A.t0 + k, sched_at<SC>(A, A.t0 + k));
+  int snext = sched_at<SC>(A, A.t0 + P);  // SC: the slice of the next epoch to fetch
 
   for (int tb = A.t0; tb < A.t1; tb += P) {"""
 PATCHES["elem_wait0"] = [(_ELEM_PRE, _ELEM_PRE.replace("\n\n  for (int tb", "\n  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)\n\n  for (int tb"))]
@@ -99,8 +99,8 @@ PATCHES["diag_consp_loadonly"] = [(
 # register tuple right after issuing it and waited vmcnt(0) each epoch: c4
 # bonds 1.25 -> 1.58. The reciprocal is now its own 4-byte load.)
 # element-wise scan: unconditional clamped ring refill alone (round 5: c2 1.54 -> 1.56, c4 1.27 -> 1.41, rejected)
-PATCHES["elem_refill_clamped"] = [("      if (t + P < A.t1) {\n        fetch(k, t + P, snext);\n        if constexpr (SC) snext = sched_at(t + P + 1);",
-                                   "      {\n        fetch(k, min(t + P, A.t1 - 1), snext);\n        if constexpr (SC) snext = sched_at(t + P + 1);")]
+PATCHES["elem_refill_clamped"] = [("      if (t + P < A.t1) {\n        fetch(k, t + P, snext);\n        if constexpr (SC) snext = sched_at<SC>(A, t + P + 1);",
+                                   "      {\n        fetch(k, min(t + P, A.t1 - 1), snext);\n        if constexpr (SC) snext = sched_at<SC>(A, t + P + 1);")]
 
 # ---------------------------------------------------------------------------
 # Round 6: YumaRust's strip scan k_bonds_cn. Timing-only

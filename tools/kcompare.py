@@ -11,7 +11,9 @@ kernel left without a partner is printed. With --all, every other kernel is
 still compared under its unchanged name.
 k_bonds_elem's trailing history element type (HT = float, the default) is
 dropped from a name before the two sides are matched, so that a library built
-before that parameter existed pairs with one built after."""
+before that parameter existed pairs with one built after.
+A k_bonds_elem<VARIANT, SH, FORM> name is printed with its form word as bit
+names behind it, [VEC|RQ|...] (elem_form, form_names)."""
 import hashlib
 import os
 import re
@@ -24,6 +26,35 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 FIELDS = ("vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
           "group_segment_fixed_size", "kernarg_segment_size")
 TAIL = "EEvNS_8BondArgsE"
+EF = ("VEC", "RQ", "U16", "HS", "BF16", "SC", "MV", "RL", "RW", "RS")  # k_bonds_elem's form word, bit 0 first (yk::EF_*)
+ELEM = re.compile(r"k_bonds_elemILi(\d)ENS_9ElemShapeI(.*?)EEELj(\d+)E(?=EEvNS_8ElemArgsI)")
+
+
+def elem_form(name):
+    """(variant, shape arguments, form word) of a k_bonds_elem<VARIANT, SH, FORM> name, else None"""
+    m = ELEM.search(name)
+    return (m.group(1), m.group(2), int(m.group(3))) if m else None
+
+
+def form_names(form):
+    return "|".join(n for i, n in enumerate(EF) if form >> i & 1) or "0"
+
+
+def elem_forms(names, bit):
+    """the k_bonds_elem names whose form word has the bit (a name of EF): name -> (variant, shape, form)"""
+    return {k: f for k, f in ((k, elem_form(k)) for k in names) if f and f[2] >> EF.index(bit) & 1}
+
+
+def with_form(name, clear, add=None):
+    """the name with bit `clear` of its form word cleared and bit `add` set: a form's twin"""
+    m = ELEM.search(name)
+    form = int(m.group(3)) & ~(1 << EF.index(clear)) | (1 << EF.index(add) if add else 0)
+    return f"{name[:m.start(3)]}{form}{name[m.end(3):]}"
+
+
+def show(name):
+    f = elem_form(name)
+    return f"{name} [{form_names(f[2])}]" if f else name
 
 
 def kernels(lib, every=False):
@@ -55,6 +86,8 @@ def kernels(lib, every=False):
 
 
 def key(name):
+    # (One rewrite per template parameter k_bonds_elem once gained. From the form word on (<VARIANT, SH, FORM>) a
+    # new option is a new bit and changes no existing name: no further rewrite is needed.)
     # <..., RW, RL> takes conditional_t<SH::RS, BondArgsRs, ElemArgs<SC, MV, RW, RL>>: the name of before the row
     # summary (an ElemShapeRs shape, BondArgsRs: only in a library that has it)
     name = re.sub(r"EEEvNSt11conditionalIXsrT0_2RSENS_10BondArgsRsENS\d+_(IXT8_ENS_10BondArgsRwE.*)E4typeE$",
@@ -117,11 +150,11 @@ def main():
     print(f"  machine code differs: {len(code)}")
     print(f"  only in the first: {len(set(A) - set(B))}")
     for k in sorted(set(meta) | set(code)):
-        print("DIFF", k, A[k], B[k])
+        print("DIFF", show(k), A[k], B[k])
     head = "code " + " ".join(f.replace("_count", "").replace("_fixed_size", "").replace("_segment", "") for f in FIELDS)
     print(f"only in the second ({len(set(B) - set(A))}): {head}")
     for k in sorted(set(B) - set(A)):
-        print(" ", k, B[k][0], *B[k][2])
+        print(" ", show(k), B[k][0], *B[k][2])
     if "--by-code" in sys.argv:
         pairs, la, lb = pair_by_code(A, B)
         scans = lambda D: sum(1 for k in D if re.search(r"k_bonds|k_rust_big", k))
@@ -130,16 +163,16 @@ def main():
         print(f"bond scans paired by code (byte-identical, equal metadata): {len(pairs)}; "
               f"without a partner: {len(la)} of the first library, {len(lb)} of the second")
         for k in la:
-            print("UNPAIRED first ", k, A[k][0], *A[k][2])
+            print("UNPAIRED first ", show(k), A[k][0], *A[k][2])
         for k in lb:
-            print("UNPAIRED second", k, B[k][0], *B[k][2])
+            print("UNPAIRED second", show(k), B[k][0], *B[k][2])
         if "-v" in sys.argv:
             for x, y in pairs:
-                print("  PAIR", x, "\n      ", y)
+                print("  PAIR", show(x), "\n      ", show(y))
     if "-v" in sys.argv:
         print(f"in both: {head}")
         for k in both:
-            print(" ", k, A[k][0], *A[k][2])
+            print(" ", show(k), A[k][0], *A[k][2])
 
 
 if __name__ == "__main__":

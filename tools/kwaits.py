@@ -1,6 +1,8 @@
-"""The vector-memory waits of k_bonds_elem's event forms, from the library's
-gfx950 code object (no GPU needed): the RL (reset event) forms beside their
-plain twins, and the RW (validator-row event) forms beside their RL twins.
+"""The vector-memory waits of k_bonds_elem's event and summary forms, from the
+library's gfx950 code object (no GPU needed): the RL (reset event) and RS (row
+summary) forms beside their plain twins, and the RW (validator-row event) forms
+beside their RL twins; a twin is the same name with the bit of the form word
+cleared, or RW -> RL (kcompare.elem_forms, with_form).
 For each pair it prints the s_waitcnt vmcnt(N) instructions inside the epoch
 loop and outside it, the byte and dword loads, and the register report (VGPRs,
 SGPRs, spills, scratch). The epoch loop is the largest backward-branch range
@@ -21,9 +23,11 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kcompare  # noqa: E402
 
-RL_TAIL = "Lb1EEEvNSt11conditionalIXT8"
-# <.., RW = true, RL = false>: the row-event forms (the scan with both tables), each beside its RL twin
-RW_TAIL, RW_TWIN = "Lb1ELb0EEEvNSt11conditionalIXT8", "Lb0ELb1EEEvNSt11conditionalIXT8"
+# The forms with a bit of k_bonds_elem's form word, each beside its twin: (title, bit, the twin's bit or None for
+# the bit cleared, the twin's tag)
+PAIRS = (("RL forms and their plain twins: s_waitcnt vmcnt(N) in the epoch loop and outside it;", "RL", None, "plain"),
+         ("RW forms (validator-row events: both tables) and their RL twins", "RW", "RL", "RL   "),
+         ("RS forms (the per-validator bond summary) and their plain twins", "RS", None, "plain"))
 
 
 def disassemble(lib):
@@ -113,37 +117,19 @@ def waits(ins, name):
 def main():
     lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(kcompare.ROOT, "yuma-simulation_amd", "lib", "libyuma_hip.so")
     code, meta = disassemble(lib), kcompare.kernels(lib)
-    print("k_bonds_elem RL forms and their plain twins: s_waitcnt vmcnt(N) in the epoch loop and outside it;")
-    print("registers: " + " ".join(kcompare.FIELDS))
-    for name in sorted(code):
-        if "k_bonds_elem" not in name or RL_TAIL not in name:
-            continue
-        twin = name.replace(RL_TAIL, RL_TAIL.replace("Lb1", "Lb0", 1))
-        s = re.search(r"k_bonds_elemILi(\d)ENS_9ElemShapeI(.*?)EEE(.*?)EEvN", name)
-        print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
-        for tag, k in (("RL   ", name), ("plain", twin)):
-            print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
-    print()
-    print("k_bonds_elem RW forms (validator-row events: both tables) and their RL twins")
-    for name in sorted(code):
-        if "k_bonds_elem" not in name or RW_TAIL not in name:
-            continue
-        twin = name.replace(RW_TAIL, RW_TWIN)
-        s = re.search(r"k_bonds_elemILi(\d)ENS_9ElemShapeI(.*?)EEE(.*?)EEvN", name)
-        print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
-        for tag, k in (("RW   ", name), ("RL   ", twin)):
-            print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
-    print()
-    print("k_bonds_elem RS forms (the per-validator bond summary: an ElemShapeRs shape) and their plain twins")
-    for name in sorted(code):
-        if "k_bonds_elem" not in name or "ElemShapeRsI" not in name:
-            continue
-        twin = name.replace("ENS_11ElemShapeRsI", "ENS_9ElemShapeI")
-        s = re.search(r"k_bonds_elemILi(\d)ENS_11ElemShapeRsI(.*?)EEE(.*?)EEvN", name)
-        print(f"variant {s.group(1)} shape {s.group(2)} flags {s.group(3)}")
-        for tag, k in (("RS   ", name), ("plain", twin)):
-            if k in code:
-                print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
+    for n, (title, bit, twin_bit, twin_tag) in enumerate(PAIRS):
+        if n:
+            print()
+        print("k_bonds_elem " + title)
+        if not n:
+            print("registers: " + " ".join(kcompare.FIELDS))
+        forms = kcompare.elem_forms(code, bit)
+        for name in sorted(forms, key=lambda k: forms[k]):
+            variant, shape, form = forms[name]
+            print(f"variant {variant} shape {shape} form {kcompare.form_names(form)}")
+            for tag, k in ((f"{bit}   ", name), (twin_tag, kcompare.with_form(name, bit, twin_bit))):
+                if k in code:
+                    print(f"  {tag} {waits(code[k], k)}  regs {' '.join(meta[k][2])}")
 
 
 if __name__ == "__main__":

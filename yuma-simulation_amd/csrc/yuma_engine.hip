@@ -3224,7 +3224,7 @@ __global__ __launch_bounds__(256) void k_incentive(float* __restrict__ Rio,
 // dpart[slice][tile][v] = sum over the tile's columns of B_state * I.
 // ---------------------------------------------------------------------------
 struct BondArgs {
-  const float* W;  // k_bonds_elem<.., WT = uint16_t>: uint16 elements behind this pointer
+  const float* W;  // k_bonds_elem under EF_U16: uint16 elements behind this pointer
   const float* rsd;
   const float* sn;
   const float* C;
@@ -3260,7 +3260,7 @@ struct BondArgs {
   int hstride, hnext, hslot;
   // bfloat16 history (YUMA_RUN_HIST_BF16): B_hist addresses __bf16 elements in
   // the same [slot][N][V][M] layout. Read on the host only: plan_scan
-  // picks the HT = __bf16 instantiation of k_bonds_elem from it, no kernel
+  // picks the EF_BF16 form of k_bonds_elem from it, no kernel
   // tests it. The word fills what was the record's tail padding (20 pointers
   // and 13 ints left 4 bytes), so sizeof(BondArgs), every other field's offset
   // and with them every existing kernel's argument block and code stay as they
@@ -3268,38 +3268,79 @@ struct BondArgs {
   int hbf16;
 };
 static_assert(sizeof(BondArgs) == 216, "hbf16 sits in the former tail padding: the argument block keeps its size");
-// ... under an input schedule (k_bonds_elem<.., SC = true>)
-struct BondArgsSc : BondArgs {
+// The form word of k_bonds_elem: one bit per option of the scan (the comment
+// above the kernel describes each; elem_form_ok there says which words exist).
+// A new option is a new bit: it changes no existing instantiation's name.
+constexpr unsigned EF_VEC = 1u << 0;   // vector form (float4 / 8-byte accesses)
+constexpr unsigned EF_RQ = 1u << 1;    // k_rowsum's screened reciprocals (rq4)
+constexpr unsigned EF_U16 = 1u << 2;   // uint16 W (WT = uint16_t)
+constexpr unsigned EF_HS = 1u << 3;    // strided history
+constexpr unsigned EF_BF16 = 1u << 4;  // bfloat16 history (HT = __bf16)
+constexpr unsigned EF_SC = 1u << 5;    // input schedule
+constexpr unsigned EF_MV = 1u << 6;    // per-epoch bond movement
+constexpr unsigned EF_RL = 1u << 7;    // reset events: the column table alone
+constexpr unsigned EF_RW = 1u << 8;    // validator-row events: the column table and the row table
+constexpr unsigned EF_RS = 1u << 9;    // per-validator bond summary
+constexpr bool ef(unsigned form, unsigned bits) { return (form & bits) != 0; }
+constexpr unsigned ef_if(bool on, unsigned bits) { return on ? bits : 0u; }
+// What a form appends to BondArgs, in this order
+struct ArgsSc {          // EF_SC
   const int32_t* sched;  // [E] device memory: epoch t reads stored slice sched[t]
   int K;                 // stored slices
 };
-// ... with the per-epoch bond movement (k_bonds_elem<.., MV = true>), and both
-struct BondArgsMv : BondArgs {
+struct ArgsMv {    // EF_MV
   float* B_move;  // [E][N][2], zeroed before the run's first scan (k_move_zero)
 };
-struct BondArgsScMv : BondArgsSc {
-  float* B_move;
-};
-// ... with reset events (k_bonds_elem<.., RL = true>): the resolved table
-struct BondArgsRl : BondArgs {
+struct ArgsRl {                // EF_RL or EF_RW
   const unsigned char* rmask;  // [E][N][ceil(M / 8)]: bit c & 7 of byte c >> 3 set = column c is zeroed (k_reset_events)
 };
-// ... and with validator-row events beside them (k_bonds_elem<.., RW = true, RL = false>): the second table
-struct BondArgsRw : BondArgsRl {
+struct ArgsRw {             // EF_RW
   const unsigned* rowmask;  // [E][N][V] 32-bit words: non-zero = bond row v is zeroed (k_row_events)
 };
-template <bool SC, bool MV, bool RW = false, bool RL = false>
-using ElemArgs = std::conditional_t<RW, BondArgsRw,
-                                    std::conditional_t<RL, BondArgsRl,
-                                                       std::conditional_t<MV, std::conditional_t<SC, BondArgsScMv, BondArgsMv>,
-                                                                          std::conditional_t<SC, BondArgsSc, BondArgs>>>>;
-// ... with the per-validator bond summary (k_bonds_elem<.., RS = true>)
-struct BondArgsRs : BondArgs {
+struct ArgsRs {      // EF_RS
   float* B_rowstat;  // [E][N][V][3], zeroed before the run's first scan (k_move_zero)
   float* tpart;      // the I = 1 twin of dpart (DP_QTE), from the workspace
 };
+template <typename T>
+struct NoArgs {};  // the empty base of a part the form lacks
+template <bool ON, typename T>
+using ArgsIf = std::conditional_t<ON, T, NoArgs<T>>;
+// k_bonds_elem<.., FORM>'s argument record: BondArgs and the parts of the form
+template <unsigned FORM>
+struct ElemArgs : BondArgs,
+                  ArgsIf<ef(FORM, EF_SC), ArgsSc>,
+                  ArgsIf<ef(FORM, EF_MV), ArgsMv>,
+                  ArgsIf<ef(FORM, EF_RL | EF_RW), ArgsRl>,
+                  ArgsIf<ef(FORM, EF_RW), ArgsRw>,
+                  ArgsIf<ef(FORM, EF_RS), ArgsRs> {};
+// Every argument block keeps its bytes, and with them every instantiation its code
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winvalid-offsetof"
+static_assert(sizeof(ElemArgs<0>) == 216 && sizeof(ElemArgs<EF_VEC | EF_RQ | EF_U16 | EF_HS | EF_BF16>) == 216);
+static_assert(sizeof(ElemArgs<EF_SC>) == 232 && offsetof(ElemArgs<EF_SC>, sched) == 216 && offsetof(ElemArgs<EF_SC>, K) == 224);
+static_assert(sizeof(ElemArgs<EF_MV>) == 224 && offsetof(ElemArgs<EF_MV>, B_move) == 216);
+static_assert(sizeof(ElemArgs<EF_SC | EF_MV>) == 240 && offsetof(ElemArgs<EF_SC | EF_MV>, sched) == 216 &&
+              offsetof(ElemArgs<EF_SC | EF_MV>, K) == 224 && offsetof(ElemArgs<EF_SC | EF_MV>, B_move) == 232);
+static_assert(sizeof(ElemArgs<EF_RL>) == 224 && offsetof(ElemArgs<EF_RL>, rmask) == 216);
+static_assert(sizeof(ElemArgs<EF_RW>) == 232 && offsetof(ElemArgs<EF_RW>, rmask) == 216 && offsetof(ElemArgs<EF_RW>, rowmask) == 224);
+static_assert(sizeof(ElemArgs<EF_RS>) == 232 && offsetof(ElemArgs<EF_RS>, B_rowstat) == 216 && offsetof(ElemArgs<EF_RS>, tpart) == 224);
+#pragma clang diagnostic pop
 __host__ __device__ __forceinline__ bool hist_strided(const BondArgs& A) {
   return A.hstride != 1 || A.hnext != A.t0 || A.hslot != A.t0;
+}
+// SC: the stored slice of epoch t under the input schedule of A (its sched and
+// K), 0 without one: t clamped to the launch's last epoch, so that a read-ahead
+// stays inside the schedule's E entries; block-uniform, a scalar load through
+// the constant address space, clamped into [0, K)
+template <bool SC, typename Args>
+__device__ __forceinline__ int sched_at(const Args& A, int t) {
+  if constexpr (SC) {
+    typedef const __attribute__((address_space(4))) int32_t* cptr;
+    const int tt = __builtin_amdgcn_readfirstlane(min(t, A.t1 - 1));
+    return min(max(__builtin_amdgcn_readfirstlane(((cptr)A.sched)[tt]), 0), A.K - 1);
+  } else {
+    return 0;
+  }
 }
 
 // Dividend partials. Each bond scan forms p_k = sum over tile k's columns of
@@ -4092,9 +4133,11 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // quads run along a row (CB/4 lanes per row), so a wave instruction moves
 // 4 rows x 256 B (CB = 64) or 1 row x 1 KiB (CB >= 256). The dividend partial
 // of each 64-miner tile is the 16-lane DPP sum of one DPP row in every shape.
-// HS: the strided history (BondArgs::hnext; B_hist is not null). A template
-// parameter, so that the dense-history and history-less scans keep their code.
-// HT: the history's element type, float or __bf16 (BondArgs::hbf16). A bf16
+// FORM: the form word, a mask of EF_ bits (at BondArgs); VEC, RQ, HS, SC, MV,
+// RW, RS below are its bits as the kernel's constants, WT, HT and RL derived.
+// HS: the strided history (BondArgs::hnext; B_hist is not null). A bit of the
+// form, so that the dense-history and history-less scans keep their code.
+// HT: the history's element type, __bf16 under EF_BF16 (BondArgs::hbf16), else float. A bf16
 // history stores RNE(B) of the lane's four fp32 bond values (v_cvt_pk_bf16_f32;
 // a NaN stays a NaN) as one 8-byte non-temporal vector; the state, the
 // dividend partials and Bstate are formed from the fp32 registers, so every
@@ -4108,8 +4151,8 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // prefetch ring; the schedule is not written while a run is in flight),
 // clamped into [0, K) with scalar min / max, and read one fetch ahead so that
 // no fetch waits for it. BondArgs has no room for the two words: the SC
-// instantiations take BondArgsSc, the record with the two appended, and every
-// other instantiation keeps its argument block and its code.
+// forms' record has the two appended (ArgsSc), and every other form keeps its
+// argument block and its code.
 // MV: the per-epoch bond movement (yuma_run_move). B_move[t][n][0] is the
 // maximum over (v, m) of |B_t - B_{t-1}|, B_move[t][n][1] that of |B_t|, B_t
 // the state after epoch t (the bits a dense fp32 history holds; a reset at
@@ -4125,9 +4168,8 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // is full or the launch ends: one
 // returnless unsigned max atomic per maximum, wave and epoch, to B_move,
 // which the engine has zeroed (k_move_zero). A maximum is order-
-// independent, so the result is bit-defined. The MV instantiations take
-// BondArgsMv / BondArgsScMv, the records with the pointer appended; every
-// other instantiation keeps its argument block and its code.
+// independent, so the result is bit-defined. The MV forms' record has the
+// pointer appended (ArgsMv); every other form keeps its argument block and its code.
 // RL: reset events (yuma_run_resets). k_reset_events has resolved every event
 // of the chunk into the table rmask, one bit per (epoch, scenario, column),
 // bytes [E][N][ceil(M / 8)]: both of an event's conditions (a bond state
@@ -4137,16 +4179,14 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // (first: loads return in order, and it is the first value an epoch reads),
 // and at the top of the epoch every row of the lane is cleared branch-free
 // (B = bit ? 0 : B, as an AND mask), never a load in the loop's rare path
-// (which would drain the ring, see zero_c below). The RL instantiations take
-// BondArgsRl, the record with the table pointer appended; every other
-// instantiation keeps its argument block and its code. Yuma 3 / Yuma 4 in
+// (which would drain the ring, see zero_c below). The RL forms' record has the
+// table pointer appended (ArgsRl); every other form keeps its argument block
+// and its code. EF_RL is this table alone. Yuma 3 / Yuma 4 in
 // vector form with fp32 weights and an fp32 history or none, no schedule and
 // no movement: the four shapes plan_scan picks there.
-// RW: validator-row events beside them (yuma_run_events): a further form of
-// the same scan, the one with both tables. It stands before RL in the
-// parameter list and is instantiated as <.., RW = true, RL = false>, so that
-// the RL forms keep "RL = true" as their last template argument; inside the
-// kernel RL means "the column table is read", which RW implies.
+// RW (EF_RW): validator-row events beside them (yuma_run_events): a further
+// form of the same scan, the one with both tables. Inside the kernel RL means
+// "the column table is read", EF_RL or EF_RW.
 // k_row_events has resolved the chunk's row events into the table rowmask, one
 // 32-bit word per (epoch, scenario, validator), the index of rsd and sn: zero
 // keeps the row, a set word zeroes it. A lane owns R rows (row0 + G * i), so
@@ -4155,9 +4195,9 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // in vector registers for the reasons given there; at the top of the epoch
 // row i's four values are ANDed with the complement of its word. A run with
 // row events always takes this form, on an all-zero column table where it has
-// no column events. The RW instantiations take BondArgsRw, BondArgsRl with the
-// second pointer appended.
-// RS (SH::RS, the shape an ElemShapeRs): the per-validator bond summary
+// no column events. The RW forms' record has the second pointer appended
+// behind the first (ArgsRw).
+// RS: the per-validator bond summary
 // (yuma_run_rowstat), B_rowstat[t][n][v][3].
 // [0] and [1] are MV's two maxima taken over the row v alone: the same bit
 // masks and unsigned maxima, one pair per row of the lane. In the flat shapes
@@ -4175,9 +4215,9 @@ __global__ __launch_bounds__(256) void k_rust_big_norm(BondArgs A, int t, const 
 // joined (S_g sequential over b = g mod 4, then ((S_0 + S_1) + S_2) + S_3) and
 // stores the total. So the bits depend neither on the flat shape nor on the
 // chunking. Yuma 3 / Yuma 4 in vector form, fp32 weights, screened
-// reciprocals, no history, schedule, movement or events. The RS
-// instantiations take BondArgsRs, BondArgs with the two pointers appended;
-// every other instantiation keeps its argument block and its code.
+// reciprocals, no history, schedule, movement or events. The RS forms' record
+// has the two pointers appended (ArgsRs); every other form keeps its argument
+// block and its code.
 // SH: the block shape, an ElemShape (R, P, BS, CB as above; VECI: float4
 // incentive / bond_alpha loads; NT: non-temporal history stores; DPL: the
 // dividend-partial layout).
@@ -4185,36 +4225,35 @@ template <int R_, int P_, bool VECI_, bool NT_, int BS_, int CB_, int DPL_>
 struct ElemShape {
   static constexpr int R = R_, P = P_, BS = BS_, CB = CB_, DPL = DPL_;
   static constexpr bool VECI = VECI_, NT = NT_;
-  static constexpr bool RS = false;
 };
-// The same shape with the row summary (RS above). The flag rides on the shape's
-// type, not on k_bonds_elem's parameter list, so that the names of the other
-// forms keep their tail: the last two template arguments stay RW and RL.
-template <int R_, int P_, bool VECI_, bool NT_, int BS_, int CB_, int DPL_>
-struct ElemShapeRs : ElemShape<R_, P_, VECI_, NT_, BS_, CB_, DPL_> {
-  static constexpr bool RS = true;
-};
-template <int VARIANT, typename SH, bool VEC, bool RQ = false, typename WT = float, bool HS = false,
-          typename HT = float, bool SC = false, bool MV = false, bool RW = false, bool RL_ = false>
-__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SH::RS, BondArgsRs, ElemArgs<SC, MV, RW, RL_>> A) {
-  static_assert(!(RW && RL_), "row events: <.., RW = true, RL = false> is the scan with both tables");
-  constexpr bool RL = RL_ || RW;  // the column table is read
-  constexpr bool RS = SH::RS;     // the row summary: a property of the shape's type (ElemShapeRs)
+// Which forms exist: the options beyond VEC, RQ, U16 and HS are Yuma 3 / Yuma 4
+// in vector form, each with what it excludes.
+constexpr bool elem_form_ok(int variant, bool nt, int dpl, unsigned form) {
+  const bool y34vec = variant >= YUMA_VARIANT_YUMA3 && ef(form, EF_VEC), flat = dpl == DP_QTE;
+  // bf16 history: non-temporal stores, no screened reciprocal
+  if (ef(form, EF_BF16) && !(y34vec && nt && !ef(form, EF_RQ))) return false;
+  if (ef(form, EF_SC) && !y34vec) return false;  // input schedules
+  // bond movement: the history-less flat shapes
+  if (ef(form, EF_MV) && !(y34vec && flat && !ef(form, EF_BF16 | EF_HS))) return false;
+  // reset events, either table: fp32 weights and history, no schedule, no movement
+  if (ef(form, EF_RL | EF_RW) && !(y34vec && !ef(form, EF_U16 | EF_BF16 | EF_SC | EF_MV))) return false;
+  // row summary: fp32 weights, the history-less flat shapes with the screened reciprocal alone
+  if (ef(form, EF_RS) && !(y34vec && flat && ef(form, EF_RQ) &&
+                           !ef(form, EF_U16 | EF_BF16 | EF_HS | EF_SC | EF_MV | EF_RL | EF_RW)))
+    return false;
+  return true;
+}
+template <int VARIANT, typename SH, unsigned FORM>
+__global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(ElemArgs<FORM> A) {
+  constexpr bool VEC = FORM & EF_VEC, RQ = FORM & EF_RQ, HS = FORM & EF_HS, SC = FORM & EF_SC, MV = FORM & EF_MV;
+  constexpr bool RW = FORM & EF_RW, RS = FORM & EF_RS;
+  constexpr bool RL = FORM & (EF_RL | EF_RW);  // the column table is read
+  using WT = std::conditional_t<ef(FORM, EF_U16), uint16_t, float>;
+  using HT = std::conditional_t<ef(FORM, EF_BF16), __bf16, float>;
   constexpr int R = SH::R, P = SH::P, BS = SH::BS, CB = SH::CB, DPL = SH::DPL;
   constexpr bool VECI = SH::VECI, NT = SH::NT;
-  static_assert(!RS || (VEC && RQ && DPL == DP_QTE && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float> &&
-                        std::is_same_v<HT, float> && !HS && !SC && !MV && !RL),
-                "row summary: Yuma 3 / Yuma 4, vector form, fp32 weights, the history-less flat shapes alone");
+  static_assert(elem_form_ok(VARIANT, NT, DPL, FORM), "no such form of the scan: see elem_form_ok");
   constexpr bool OLD = MV || RS;  // the row's old values are kept past the update
-  static_assert(!MV || (VEC && DPL == DP_QTE && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<HT, float> && !HS),
-                "bond movement: Yuma 3 / Yuma 4, vector form, the history-less flat shapes");
-  static_assert(!SC || (VEC && VARIANT >= YUMA_VARIANT_YUMA3), "input schedules: Yuma 3 / Yuma 4, vector form");
-  static_assert(!RL || (VEC && VARIANT >= YUMA_VARIANT_YUMA3 && std::is_same_v<WT, float> && std::is_same_v<HT, float> &&
-                        !SC && !MV),
-                "reset events: Yuma 3 / Yuma 4, vector form, fp32 weights and history, no schedule, no movement");
-  static_assert(std::is_same_v<HT, float> || (std::is_same_v<HT, __bf16> && NT && VEC && !RQ &&
-                                              VARIANT >= YUMA_VARIANT_YUMA3),
-                "bf16 history: Yuma 3 / Yuma 4, vector form, non-temporal stores");
   constexpr int LPR = CB / 4, G = BS / LPR;
   static_assert(CB % 64 == 0 && BS % LPR == 0, "a 16-lane DPP row must cover one 64-miner tile");
   const int cq = threadIdx.x % LPR, lane = threadIdx.x & 63;
@@ -4349,17 +4388,6 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SH:
   // a duplicate scenario of a rank class reads its representative's column sums
   // (the rank pass skips duplicate slices; k_incentive copies R, not csb / csr)
   const int ncs = (COLNORM && A.csrep != nullptr) ? A.csrep[n] : n;
-  // SC: the stored slice of epoch t (t clamped to the launch's last epoch, so
-  // the read-ahead stays inside the schedule's E entries)
-  auto sched_at = [&](int t) -> int {
-    if constexpr (SC) {
-      typedef const __attribute__((address_space(4))) int32_t* cptr;
-      const int tt = __builtin_amdgcn_readfirstlane(min(t, A.t1 - 1));
-      return min(max(__builtin_amdgcn_readfirstlane(((cptr)A.sched)[tt]), 0), A.K - 1);
-    } else {
-      return 0;
-    }
-  };
   auto fetch = [&](int k, int t, int sk) {
     const long long slice = (long long)t * N + n;
     const long long cslice = (long long)t * N + ncs;
@@ -4422,8 +4450,8 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SH:
   long long hsl = HS ? (long long)A.hslot * N + n : 0;
 #pragma unroll
   for (int k = 0; k < P; ++k)
-    if (A.t0 + k < A.t1) fetch(k, A.t0 + k, sched_at(A.t0 + k));
-  int snext = sched_at(A.t0 + P);  // SC: the slice of the next epoch to fetch
+    if (A.t0 + k < A.t1) fetch(k, A.t0 + k, sched_at<SC>(A, A.t0 + k));
+  int snext = sched_at<SC>(A, A.t0 + P);  // SC: the slice of the next epoch to fetch
 
   for (int tb = A.t0; tb < A.t1; tb += P) {
 #pragma unroll
@@ -4751,7 +4779,7 @@ __global__ __launch_bounds__(SH::BS, 1) void k_bonds_elem(std::conditional_t<SH:
       if (YUMA2) have_wp = true;
       if (t + P < A.t1) {
         fetch(k, t + P, snext);
-        if constexpr (SC) snext = sched_at(t + P + 1);
+        if constexpr (SC) snext = sched_at<SC>(A, t + P + 1);
       }
     }
     if constexpr (RS) {
@@ -4972,7 +5000,8 @@ __global__ __launch_bounds__(256) void k_sched_expand(ExpandArgs X) {
 // ---------------------------------------------------------------------------
 constexpr int kWatchP = 8;    // epochs of inputs in flight
 constexpr int kWatchBS = 64;  // threads per block: one wave
-struct WatchArgs {
+// The argument record of k_bonds_watch and of k_bonds_rows (below)
+struct ListArgs {
   const void* W;  // fp32 or (WT = uint16_t) uint16 elements; [E][N][V][M], or [K][N][V][M] under SC
   const float* rsd;
   const float* sn;
@@ -4981,24 +5010,24 @@ struct WatchArgs {
   const yuma_params_t* prm;
   const float* B_init;
   const float* Bstate;   // [N][V][M], the state before epoch t0 when t0 > 0
-  const int32_t* watch;  // [nw] device memory
-  float* B_watch;        // [n_hist][N][V][nw]
+  const int32_t* list;   // [nl] device memory: the watched columns / rows
+  float* out;            // B_watch [n_hist][N][V][nl] / B_rows [n_hist][N][nl][M]
   const int32_t* sched;  // SC: [E] device memory
   int K;                 // SC: stored slices
-  int N, V, M, nw, t0, t1;
-  int bps;  // blocks per scenario
+  int N, V, M, nl, t0, t1;
+  int bpu;  // blocks per scenario (watch) / per watched row (rows)
   int hstride, hnext, hslot;
 };
 template <int VARIANT, typename WT, bool SC>
-__global__ __launch_bounds__(kWatchBS) void k_bonds_watch(WatchArgs A) {
+__global__ __launch_bounds__(kWatchBS) void k_bonds_watch(ListArgs A) {
   static_assert(VARIANT == YUMA_VARIANT_YUMA3 || VARIANT == YUMA_VARIANT_YUMA4, "element-wise variants only");
   constexpr int P = kWatchP;
-  const int N = A.N, V = A.V, M = A.M, nw = A.nw;
-  const int n = blockIdx.x / A.bps;
-  const long long e = (long long)(blockIdx.x % A.bps) * kWatchBS + threadIdx.x;
+  const int N = A.N, V = A.V, M = A.M, nw = A.nl;
+  const int n = blockIdx.x / A.bpu;
+  const long long e = (long long)(blockIdx.x % A.bpu) * kWatchBS + threadIdx.x;
   if (e >= (long long)V * nw) return;
   const int v = (int)(e / nw), j = (int)(e - (long long)v * nw);
-  const int col = min(max(A.watch[j], 0), M - 1);
+  const int col = min(max(A.list[j], 0), M - 1);
   const long long VM = (long long)V * M;
   const yuma_params_t& pg = A.prm[n];
   const bool liquid = pg.liquid_mode != YUMA_LIQUID_OFF;
@@ -5019,17 +5048,6 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_watch(WatchArgs A) {
 
   WT rw[P];
   float rd[P], rsn[P], rba[P];
-  // SC: the stored slice of epoch t, as k_bonds_elem reads it (block-uniform,
-  // a scalar load, clamped into [0, K), t clamped to the launch's last epoch)
-  auto sched_at = [&](int t) -> int {
-    if constexpr (SC) {
-      typedef const __attribute__((address_space(4))) int32_t* cptr;
-      const int tt = __builtin_amdgcn_readfirstlane(min(t, A.t1 - 1));
-      return min(max(__builtin_amdgcn_readfirstlane(((cptr)A.sched)[tt]), 0), A.K - 1);
-    } else {
-      return 0;
-    }
-  };
   auto fetch = [&](int k, int t, int sk) {
     const long long slice = (long long)t * N + n;
     const long long wslice = SC ? (long long)sk * N + n : slice;
@@ -5048,8 +5066,8 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_watch(WatchArgs A) {
   // (vmcnt(0)) once per P epochs, one exposed round trip each time.
   const int tl = A.t1 - 1;
 #pragma unroll
-  for (int k = 0; k < P; ++k) fetch(k, min(A.t0 + k, tl), sched_at(A.t0 + k));
-  int snext = sched_at(A.t0 + P);
+  for (int k = 0; k < P; ++k) fetch(k, min(A.t0 + k, tl), sched_at<SC>(A, A.t0 + k));
+  int snext = sched_at<SC>(A, A.t0 + P);
 
   for (int tb = A.t0; tb < A.t1; tb += P) {
 #pragma unroll
@@ -5079,13 +5097,13 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_watch(WatchArgs A) {
         B = tmin(nb, 1.0f);
       }
       if (t == hnext) {  // from t alone: the same branch in every thread
-        A.B_watch[(hsl * V + v) * nw + j] = B;
+        A.out[(hsl * V + v) * nw + j] = B;
         hnext += A.hstride;
         hsl += N;
       }
       has_old = true;
       fetch(k, min(t + P, tl), snext);
-      if constexpr (SC) snext = sched_at(t + P + 1);
+      if constexpr (SC) snext = sched_at<SC>(A, t + P + 1);
     }
   }
 }
@@ -5122,25 +5140,8 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_watch(WatchArgs A) {
 //   B_rows[s][n][j][m ..] on a test of t alone.
 // ---------------------------------------------------------------------------
 constexpr int kRowsP = 8;  // epochs of inputs in flight
-struct RowsArgs {
-  const void* W;  // fp32 or (WT = uint16_t) uint16 elements; [E][N][V][M], or [K][N][V][M] under SC
-  const float* rsd;
-  const float* sn;
-  const float* C;
-  const float* ba;
-  const yuma_params_t* prm;
-  const float* B_init;
-  const float* Bstate;   // [N][V][M], the state before epoch t0 when t0 > 0
-  const int32_t* rows;   // [nr] device memory
-  float* B_rows;         // [n_hist][N][nr][M]
-  const int32_t* sched;  // SC: [E] device memory
-  int K;                 // SC: stored slices
-  int N, V, M, nr, t0, t1;
-  int bpr;  // blocks per row
-  int hstride, hnext, hslot;
-};
 template <int VARIANT, typename WT, bool SC, int C>
-__global__ __launch_bounds__(kWatchBS) void k_bonds_rows(RowsArgs A) {
+__global__ __launch_bounds__(kWatchBS) void k_bonds_rows(ListArgs A) {
   static_assert(VARIANT == YUMA_VARIANT_YUMA3 || VARIANT == YUMA_VARIANT_YUMA4, "element-wise variants only");
   static_assert(C == 4 || C == 1, "a quad of columns per thread, or one");
   constexpr int P = kRowsP;
@@ -5148,13 +5149,13 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_rows(RowsArgs A) {
   // a thread's weights and bond_alpha of one epoch: one vector, or one element
   using WV = std::conditional_t<C == 4, std::conditional_t<U16, usvec4, fvec4>, WT>;
   using FV = std::conditional_t<C == 4, fvec4, float>;
-  const int N = A.N, V = A.V, M = A.M, nr = A.nr;
-  const int nj = blockIdx.x / A.bpr;
+  const int N = A.N, V = A.V, M = A.M, nr = A.nl;
+  const int nj = blockIdx.x / A.bpu;
   const int n = nj / nr, j = nj - n * nr;
-  const long long m0 = ((long long)(blockIdx.x % A.bpr) * kWatchBS + threadIdx.x) * C;
+  const long long m0 = ((long long)(blockIdx.x % A.bpu) * kWatchBS + threadIdx.x) * C;
   if (m0 >= M) return;
   const int m = (int)m0;
-  const int v = min(max(A.rows[j], 0), V - 1);
+  const int v = min(max(A.list[j], 0), V - 1);
   const long long VM = (long long)V * M;
   const yuma_params_t& pg = A.prm[n];
   const bool liquid = pg.liquid_mode != YUMA_LIQUID_OFF;
@@ -5193,16 +5194,6 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_rows(RowsArgs A) {
   WV rw[P];
   FV rba[P];
   float rd[P], rsn[P];
-  // SC: the stored slice of epoch t, as k_bonds_watch reads it
-  auto sched_at = [&](int t) -> int {
-    if constexpr (SC) {
-      typedef const __attribute__((address_space(4))) int32_t* cptr;
-      const int tt = __builtin_amdgcn_readfirstlane(min(t, A.t1 - 1));
-      return min(max(__builtin_amdgcn_readfirstlane(((cptr)A.sched)[tt]), 0), A.K - 1);
-    } else {
-      return 0;
-    }
-  };
   auto fetch = [&](int k, int t, int sk) {
     const long long slice = (long long)t * N + n;
     const long long wslice = SC ? (long long)sk * N + n : slice;
@@ -5217,12 +5208,12 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_rows(RowsArgs A) {
   const int tl = A.t1 - 1;
 #pragma unroll
   for (int k = 0; k < P; ++k) {
-    fetch(k, min(A.t0 + k, tl), sched_at(A.t0 + k));
+    fetch(k, min(A.t0 + k, tl), sched_at<SC>(A, A.t0 + k));
     // the ring fills in the order the loop empties it: left to the scheduler the first slot's loads were
     // issued last, and the wait at the loop's head (the join with the back edge) became vmcnt(0)
     __builtin_amdgcn_sched_barrier(0);
   }
-  int snext = sched_at(A.t0 + P);
+  int snext = sched_at<SC>(A, A.t0 + P);
 
   // One epoch from ring slot k; FETCH: refill the slot with epoch t + P's inputs.
   auto step = [&](int k, int t, auto FETCH) {
@@ -5255,7 +5246,7 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_rows(RowsArgs A) {
       }
     }
     if (t == hnext) {  // from t alone: the same branch in every thread
-      float* const dst = A.B_rows + (hsl * nr + j) * M + m;
+      float* const dst = A.out + (hsl * nr + j) * M + m;
       if constexpr (C == 4)
         *reinterpret_cast<fvec4*>(dst) = fvec4{B[0], B[1], B[2], B[3]};
       else
@@ -5266,7 +5257,7 @@ __global__ __launch_bounds__(kWatchBS) void k_bonds_rows(RowsArgs A) {
     has_old = true;
     if constexpr (decltype(FETCH)::value) {
       fetch(k, min(t + P, tl), snext);
-      if constexpr (SC) snext = sched_at(t + P + 1);
+      if constexpr (SC) snext = sched_at<SC>(A, t + P + 1);
     }
   };
   // Whole groups of P epochs: no way out of the loop but its end. With the
@@ -6575,9 +6566,6 @@ template <bool VEC>
 using ElemFlat1 = yk::ElemShape<1, 4, VEC, false, 256, 256, yk::DP_QTE>;
 template <bool VEC>
 using ElemFlat2 = yk::ElemShape<2, kNoHistP2, VEC, false, 256, 256, yk::DP_QTE>;
-// ... and with the row summary (vector form only)
-using ElemFlat1Rs = yk::ElemShapeRs<1, 4, true, false, 256, 256, yk::DP_QTE>;
-using ElemFlat2Rs = yk::ElemShapeRs<2, kNoHistP2, true, false, 256, 256, yk::DP_QTE>;
 
 // What the choice of a scan depends on.
 struct ScanKey {
@@ -6616,7 +6604,7 @@ struct ScanPlan : yuma_scan_plan_t {
 // stride, in that shape's HS instantiation ("Strided bond history").
 // A bfloat16 history (run_plan admits it for Yuma 3 / Yuma 4 in vector form
 // without shared inputs, where a history is written from the wide or the
-// 64-miner-tile shape only) runs the same two shapes with HT = __bf16
+// 64-miner-tile shape only) runs the same two shapes under EF_BF16
 // ("bfloat16 bond history").
 // SC: the scan under an input schedule (yuma_sched_native: Yuma 3 / Yuma 4,
 // vector form, no shared inputs, k_rowsum's reciprocals at hand), in the SC
@@ -6709,13 +6697,12 @@ void launch_scan(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const int32
                  float* B_move = nullptr, const unsigned char* rmask = nullptr, const unsigned* rowmask = nullptr,
                  float* B_rowstat = nullptr, float* tpart = nullptr);
 
-// The watched columns' scan over the chunk of A (k_bonds_watch), from the main
-// scan's own arguments: the same inputs, state and history countdown. Enqueued
-// before that scan, which overwrites A.Bstate.
-template <typename WT>
-void launch_watch(hipStream_t st, int variant, const yk::BondArgs& A, const int32_t* watch, int nw, float* B_watch,
-                  const int32_t* sched, int K) {
-  yk::WatchArgs X{};
+// The arguments of a watch-list scan (k_bonds_watch, k_bonds_rows) over the
+// chunk of A, from the main scan's own: the same inputs, state and history
+// countdown; the list, its output, its length and the blocks per unit beside them.
+yk::ListArgs list_args(const yk::BondArgs& A, const int32_t* list, float* out, int nl, long long bpu,
+                       const int32_t* sched, int K) {
+  yk::ListArgs X{};
   X.W = A.W;
   X.rsd = A.rsd;
   X.sn = A.sn;
@@ -6724,21 +6711,30 @@ void launch_watch(hipStream_t st, int variant, const yk::BondArgs& A, const int3
   X.prm = A.prm;
   X.B_init = A.B_init;
   X.Bstate = A.Bstate;
-  X.watch = watch;
-  X.B_watch = B_watch;
+  X.list = list;
+  X.out = out;
   X.sched = sched;
   X.K = K;
   X.N = A.N;
   X.V = A.V;
   X.M = A.M;
-  X.nw = nw;
+  X.nl = nl;
   X.t0 = A.t0;
   X.t1 = A.t1;
-  X.bps = (int)(((long long)A.V * nw + yk::kWatchBS - 1) / yk::kWatchBS);
+  X.bpu = (int)bpu;
   X.hstride = A.hstride;
   X.hnext = A.hnext;
   X.hslot = A.hslot;
-  const long long nblocks = (long long)A.N * X.bps;
+  return X;
+}
+
+// The watched columns' scan over the chunk of A (k_bonds_watch). Enqueued
+// before the main scan, which overwrites A.Bstate.
+template <typename WT>
+void launch_watch(hipStream_t st, int variant, const yk::BondArgs& A, const int32_t* watch, int nw, float* B_watch,
+                  const int32_t* sched, int K) {
+  const yk::ListArgs X = list_args(A, watch, B_watch, nw, ((long long)A.V * nw + yk::kWatchBS - 1) / yk::kWatchBS, sched, K);
+  const long long nblocks = (long long)A.N * X.bpu;
   with_bool(sched != nullptr, [&](auto SC) {
     constexpr bool kSc = decltype(SC)::value;
     if (variant == YUMA_VARIANT_YUMA3)
@@ -6751,40 +6747,18 @@ void launch_watch(hipStream_t st, int variant, const yk::BondArgs& A, const int3
 // Blocks per watched row of k_bonds_rows with c columns per thread
 long long rows_bpr(int M, int c) { return (((long long)M + c - 1) / c + yk::kWatchBS - 1) / yk::kWatchBS; }
 
-// The watched rows' scan over the chunk of A (k_bonds_rows), from the main
-// scan's own arguments like launch_watch, and enqueued before that scan too.
+// The watched rows' scan over the chunk of A (k_bonds_rows), enqueued before
+// the main scan like launch_watch.
 // The vector form (four columns per thread) where M % 4 == 0 and W (8 bytes
 // for uint16), the old state (B_init, the state buffer), the liquid bond_alpha
 // and B_rows are on a 16-byte boundary; one column per thread elsewhere.
 template <typename WT>
 void launch_rows(hipStream_t st, int variant, const yk::BondArgs& A, const int32_t* rows, int nr, float* B_rows,
                  const int32_t* sched, int K) {
-  yk::RowsArgs X{};
-  X.W = A.W;
-  X.rsd = A.rsd;
-  X.sn = A.sn;
-  X.C = A.C;
-  X.ba = A.ba;
-  X.prm = A.prm;
-  X.B_init = A.B_init;
-  X.Bstate = A.Bstate;
-  X.rows = rows;
-  X.B_rows = B_rows;
-  X.sched = sched;
-  X.K = K;
-  X.N = A.N;
-  X.V = A.V;
-  X.M = A.M;
-  X.nr = nr;
-  X.t0 = A.t0;
-  X.t1 = A.t1;
-  X.hstride = A.hstride;
-  X.hnext = A.hnext;
-  X.hslot = A.hslot;
   const bool quad = (A.M % 4) == 0 && ((uintptr_t)A.W & (4 * sizeof(WT) - 1)) == 0 && aligned16(A.B_init) &&
                     aligned16(A.Bstate) && aligned16(A.ba) && aligned16(B_rows);
-  X.bpr = (int)rows_bpr(A.M, quad ? 4 : 1);
-  const long long nblocks = (long long)A.N * nr * X.bpr;
+  const yk::ListArgs X = list_args(A, rows, B_rows, nr, rows_bpr(A.M, quad ? 4 : 1), sched, K);
+  const long long nblocks = (long long)A.N * nr * X.bpu;
   with_bool(sched != nullptr, [&](auto SC) {
     constexpr bool kSc = decltype(SC)::value;
     with_bool(quad, [&](auto QUAD) {
@@ -7708,6 +7682,8 @@ void with_flag(const ScanPlan& p, int flag, F&& f) {
 }
 template <int MODE>
 using Mode = std::integral_constant<int, MODE>;
+template <unsigned FORM>
+using Form = std::integral_constant<unsigned, FORM>;  // a k_bonds_elem form word as a value
 
 // launch_scan for one variant, vector form, W element type and schedule flag:
 // from the plan's form, shape and flags to the instantiation. The modes
@@ -7719,28 +7695,42 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
   constexpr bool kPlain = std::is_same_v<WT, float> && !SC;  // fp32 W, no schedule
   constexpr bool kColnorm = VARIANT <= YUMA_VARIANT_YUMA2, kElem34 = VARIANT >= YUMA_VARIANT_YUMA3;
   const long long nb = p.grid;
+  // k_bonds_elem<VARIANT, SH, FORM>: the form's record from A and the parts the form has
+  constexpr unsigned kBase = yk::ef_if(VEC, yk::EF_VEC) | yk::ef_if(!std::is_same_v<WT, float>, yk::EF_U16) | yk::ef_if(SC, yk::EF_SC);
+  [[maybe_unused]] auto launch_elem = [&](auto sh, auto form) {
+    using SH = decltype(sh);
+    constexpr unsigned FORM = decltype(form)::value;
+    yk::ElemArgs<FORM> As{};
+    static_cast<yk::BondArgs&>(As) = A;
+    if constexpr (yk::ef(FORM, yk::EF_SC)) {
+      As.sched = sched;
+      As.K = K;
+    }
+    if constexpr (yk::ef(FORM, yk::EF_MV)) As.B_move = B_move;
+    if constexpr (yk::ef(FORM, yk::EF_RL | yk::EF_RW)) As.rmask = rmask;
+    if constexpr (yk::ef(FORM, yk::EF_RW)) As.rowmask = rowmask;
+    if constexpr (yk::ef(FORM, yk::EF_RS)) {
+      As.B_rowstat = B_rowstat;
+      As.tpart = tpart;
+    }
+    YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, FORM>), nb, SH::BS, st, As);
+  };
   if constexpr (kElem34 && VEC && kPlain) {
-    // reset events (RL; BondArgsRl): the four shapes plan_scan picks for Yuma 3
+    // reset events (EF_RL): the four shapes plan_scan picks for Yuma 3
     // / Yuma 4 in vector form with fp32 weights, each with the RQ it picks
     // there (the flat shapes always, the history shapes never), the history
     // shapes dense or strided, no bfloat16 history, no movement
     if (p.rl) {
       auto elem_rl = [&](auto sh, auto RQ, auto hs_mode) {
-        using SH = decltype(sh);
         constexpr bool kRq = decltype(RQ)::value;
         if ((p.rq != 0) != kRq || p.hist_bf16 || p.mv) bad_plan(p);
         with_flag<decltype(hs_mode)::value>(p, p.hs, [&](auto HS) {
-          // (RW: row events, the scan with both tables; BondArgsRw)
-          yk::BondArgsRw As{};
-          static_cast<yk::BondArgs&>(As) = A;
-          As.rmask = rmask;
-          As.rowmask = rowmask;
+          constexpr unsigned kForm = kBase | yk::ef_if(kRq, yk::EF_RQ) | yk::ef_if(decltype(HS)::value, yk::EF_HS);
+          // (EF_RW: row events, the scan with both tables)
           if (p.rw)
-            YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, kRq, float, decltype(HS)::value, float, false, false, true, false>),
-                      nb, SH::BS, st, As);
+            launch_elem(sh, Form<kForm | yk::EF_RW>{});
           else
-            YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, kRq, float, decltype(HS)::value, float, false, false, false, true>),
-                      nb, SH::BS, st, static_cast<const yk::BondArgsRl&>(As));
+            launch_elem(sh, Form<kForm | yk::EF_RL>{});
         });
       };
       if (p.form == YUMA_SCAN_ELEM) switch (p.shape) {
@@ -7757,23 +7747,18 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
     }
   }
   if constexpr (kElem34 && VEC && kPlain) {
-    // the row summary (RS; BondArgsRs): the two flat shapes with the screened
+    // the row summary (EF_RS): the two flat shapes with the screened
     // reciprocal plan_scan picks there, no history, movement or events
     if (p.rs) {
       auto elem_rs = [&](auto sh) {
-        using SH = decltype(sh);
         if (!p.rq || p.hist || p.hs || p.hist_bf16 || p.mv || p.rl || p.rw) bad_plan(p);
-        yk::BondArgsRs As{};
-        static_cast<yk::BondArgs&>(As) = A;
-        As.B_rowstat = B_rowstat;
-        As.tpart = tpart;
-        YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, true, true>), nb, SH::BS, st, As);
+        launch_elem(sh, Form<kBase | yk::EF_RQ | yk::EF_RS>{});
       };
       if (p.form == YUMA_SCAN_ELEM) switch (p.shape) {
           case YUMA_ELEM_FLAT1:
-            return elem_rs(ElemFlat1Rs{});
+            return elem_rs(ElemFlat1<true>{});
           case YUMA_ELEM_FLAT2:
-            return elem_rs(ElemFlat2Rs{});
+            return elem_rs(ElemFlat2<true>{});
         }
       bad_plan(p);
     }
@@ -7846,27 +7831,18 @@ void launch_scan_as(hipStream_t st, const ScanPlan& p, yk::BondArgs& A, const in
   if constexpr (VARIANT != YUMA_VARIANT_RUST) {
     // k_bonds_elem in the shape sh, with the plan's RQ, HS and bfloat16 history where
     // the modes admit them. sched (with SC): the input schedule and its K
-    // stored slices (BondArgsSc)
-    // mv_mode: the bond movement (B_move; BondArgsMv / BondArgsScMv), on the
+    // stored slices
+    // mv_mode: the bond movement (B_move), on the
     // flat shapes of Yuma 3 / Yuma 4 in vector form only, and there with the
     // screened reciprocal always (a run has it: plan_scan) and no history
     auto elem = [&](auto sh, auto rq_mode, auto hs_mode, auto bf16_mode, auto mv_mode) {
-      using SH = decltype(sh);
       with_flag<decltype(mv_mode)::value>(p, p.mv, [&](auto MV) {
         constexpr bool kMv = decltype(MV)::value;
         with_flag<(kMv ? kAlways : decltype(rq_mode)::value)>(p, p.rq, [&](auto RQ) {
           with_flag<(kMv ? kNever : decltype(hs_mode)::value)>(p, p.hs, [&](auto HS) {
             with_flag<(kMv ? kNever : decltype(bf16_mode)::value)>(p, p.hist_bf16, [&](auto BF16) {
-              using HT = std::conditional_t<decltype(BF16)::value, __bf16, float>;
-              constexpr bool kRq = decltype(RQ)::value, kHs = decltype(HS)::value;
-              yk::ElemArgs<SC, kMv> As{};
-              static_cast<yk::BondArgs&>(As) = A;
-              if constexpr (SC) {
-                As.sched = sched;
-                As.K = K;
-              }
-              if constexpr (kMv) As.B_move = B_move;
-              YK_LAUNCH((yk::k_bonds_elem<VARIANT, SH, VEC, kRq, WT, kHs, HT, SC, kMv>), nb, SH::BS, st, As);
+              launch_elem(sh, Form<kBase | yk::ef_if(decltype(RQ)::value, yk::EF_RQ) | yk::ef_if(decltype(HS)::value, yk::EF_HS) |
+                                   yk::ef_if(decltype(BF16)::value, yk::EF_BF16) | yk::ef_if(kMv, yk::EF_MV)>{});
             });
           });
         });
